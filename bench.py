@@ -14,6 +14,14 @@ collective (weak scaling: 1024 spectra per rank); the only collectives are the t
 and the max-over-ranks of the elapsed time, on the gloo backend (host-side: the hot path has no
 exchange step, so nothing needs RCCL).  Device buffers come from libgpdla itself, so the process
 holds a single HIP runtime (the system ROCm one the library was built against).
+
+A plain run (``--gpus 1 --steps N --warmup W``) sets up, warms up, times the N steps and prints the
+headline line (with the roofline and kernel times the engine's own HIP events give for those steps).
+``--full`` adds everything that takes work of its own: the CPU baseline, the alternatives (the int8
+path, configs[4], configs[2] resident and end to end, the widened rows; configs[3] and the
+multi-writer end-to-end run under ``--gpus N``), the panel paths' one-stream GEMM rate and the
+calc_cddf.py:246 invariant of the outputs.  ``--dump-outputs DIR`` writes the last timed step's
+outputs as ``DIR/<name>.npy`` (dump_outputs).
 """
 from __future__ import annotations
 
@@ -314,6 +322,12 @@ def run_e2e(args, world: int, rank: int, local_rank: int, dist) -> None:
         print(json.dumps(rec), flush=True)
 
 
+def default_e2e_base() -> str:
+    """Prefix of the default e2e directories: under /tmp, one per user (another user's leftover tree
+    of the same name could not be overwritten)."""
+    return f"/tmp/gpdla_e2e_{os.getuid()}"
+
+
 def e2e_record(Q: int, S: int, k: int, e2e_dir, keep: bool, world: int, rank: int, dist, dev: int):
     """configs[2] end to end: the whole process_qsos script on files --
     catalog.mat, learned_qso_model_*.mat, dla_samples.mat and preloaded_qsos.mat in (written
@@ -326,7 +340,7 @@ def e2e_record(Q: int, S: int, k: int, e2e_dir, keep: bool, world: int, rank: in
     from gp_dla_detection_amd import _lib as L
     from gp_dla_detection_amd import process as PR
     from gp_dla_detection_amd import synthetic as syn
-    base = e2e_dir or f"/tmp/gpdla_e2e_{Q}_{S}"
+    base = e2e_dir or f"{default_e2e_base()}_{Q}_{S}"
     model = syn.make_model(k=k)
     samples = syn.make_samples(S)
     t0 = time.perf_counter()
@@ -1049,7 +1063,7 @@ def e2e_alternative(args, world: int, rank: int, dist, dev: int) -> dict | None:
     computing and writing its own chunks; skipped (on every rank) when the disk under the output
     directory lacks E2E_DISK_BYTES.  Returns the record on rank 0."""
     import shutil
-    base = args.e2e_dir or "/tmp/gpdla_e2e_alt"
+    base = args.e2e_dir or f"{default_e2e_base()}_alt"
     Path(base).parent.mkdir(parents=True, exist_ok=True)
     free = shutil.disk_usage(Path(base).parent).free
     if dist is not None:
@@ -1064,6 +1078,47 @@ def e2e_alternative(args, world: int, rank: int, dist, dev: int) -> dict | None:
         rec["rehearsal"] = {"value_if_counted": rec["value"], "note": "ranks shared GPUs: not an N-GPU point"}
         rec["value"] = None
     return rec
+
+
+DUMP_SAMPLE_BYTES = 48 << 20    # --dump-outputs: cap on the sampled Q x S array (the rest is < 1 MB per 10^4 spectra)
+DUMP_SAMPLE_COLUMNS = 4096
+DUMP_TOTAL_BYTES = 64_000_000   # --dump-outputs: cap on all files of a run together (each rank gets 1/world of both caps)
+NPY_HEADER_BYTES = 128          # a .npy file's header (version 1.0, these shapes)
+
+
+def dump_outputs(out_dir, o_null, o_dla, o_s, o_n, rank: int = 0, world: int = 1) -> dict:
+    """--dump-outputs: what the timed path left in its output buffers after the last timed step (the
+    arrays Engine.process returns under the same names), as ``out_dir/<name>.npy`` in float64 (rank r > 0
+    of a multi-rank run writes ``<name>.rank<r>.npy``, and every rank has 1/world of the two caps):
+    log_likelihoods_no_dla, log_likelihoods_dla and num_pixels in full (with more than ~5.7 x 10^5 spectra
+    on a rank the same sorted default_rng(0) draw of their entries, so that the three stay within
+    DUMP_TOTAL_BYTES - DUMP_SAMPLE_BYTES); of the Q x S sample_log_likelihoods_dla a fixed sample, at most
+    DUMP_SAMPLE_BYTES: min(S, DUMP_SAMPLE_COLUMNS) columns and as many rows as fit, both drawn without
+    replacement by default_rng(0) and sorted (configs[1]: all 1,024 rows x 4,096 of the 10^4 columns).
+    The sample depends on Q, S and world alone, so two builds run with the same arguments write the same
+    entries; the files of a run together never exceed DUMP_TOTAL_BYTES.  Returns {name: shape}."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    Q, S = o_s.shape
+    sample_cap, total_cap = DUMP_SAMPLE_BYTES // world, DUMP_TOTAL_BYTES // world
+    rng = np.random.default_rng(0)
+    cols = np.sort(rng.choice(S, size=min(S, DUMP_SAMPLE_COLUMNS), replace=False))
+    rows = np.sort(rng.choice(Q, size=min(Q, max(1, sample_cap // (8 * cols.size))), replace=False))
+    sample = np.empty((rows.size, cols.size), dtype=np.float64)
+    for i, r in enumerate(rows):                    # D2H row by row: only the sampled rows cross the bus
+        sample[i] = o_s.numpy(rows=1, start=int(r))[0, cols]
+    vmax = (total_cap - sample_cap - 4 * NPY_HEADER_BYTES) // (3 * 8)   # entries per vector
+    vsel = slice(None) if Q <= vmax else np.sort(rng.choice(Q, size=vmax, replace=False))
+    arrays = {"log_likelihoods_no_dla": o_null.numpy()[vsel], "log_likelihoods_dla": o_dla.numpy()[vsel],
+              "num_pixels": o_n.numpy()[vsel].astype(np.float64), "sample_log_likelihoods_dla": sample}
+    total = 0
+    for name, a in arrays.items():
+        f = out / (f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy")
+        np.save(f, a.astype(np.float64, copy=False))
+        total += f.stat().st_size
+    if total > total_cap:
+        raise RuntimeError(f"--dump-outputs wrote {total} bytes, over this rank's cap of {total_cap}")
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def main():
@@ -1087,8 +1142,8 @@ def main():
     ap.add_argument("--panel-streams", type=int, choices=[1, 2, 3, 4], default=2,
                     help="panel-GEMM paths: compute streams a batch's spectra alternate over")
     ap.add_argument("--no-alt", action="store_true",
-                    help="skip the alternative-path measurement (fused_i8 next to the fp64 line, 1 GPU, c2)")
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU-baseline work (0 = skip)")
+                    help="--full: skip the alternative-path measurement (fused_i8 next to the fp64 line, 1 GPU, c2)")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="--full: seconds of CPU-baseline work (0 = skip)")
     ap.add_argument("--plan-only", action="store_true",
                     help="print the rank/spectrum/device layout through the launcher, no GPU call")
     ap.add_argument("--plan-devices", type=int, default=None,
@@ -1097,14 +1152,28 @@ def main():
                     help="allow N ranks on fewer than N devices (ranks share GPUs); the line then carries "
                          "value null and is labelled a rehearsal, never an N-GPU point")
     ap.add_argument("--no-configs3", action="store_true",
-                    help="skip alternatives.configs3 (the full DR12Q count split over the ranks) in a multi-rank line")
+                    help="--full: skip alternatives.configs3 (the full DR12Q count split over the ranks) in a multi-rank line")
     ap.add_argument("--no-configs2", action="store_true",
-                    help="skip alternatives.configs2 (full DR12Q count on this GPU) in the default line")
+                    help="--full: skip alternatives.configs2 (full DR12Q count on this GPU) in a 1-GPU line")
     ap.add_argument("--no-e2e", action="store_true",
-                    help="skip alternatives.e2e (configs[2] end to end on files) in the default line")
+                    help="--full: skip alternatives.e2e (configs[2] end to end on files) in a 1-GPU line")
     ap.add_argument("--no-widened", action="store_true",
-                    help="skip alternatives.dla_samples / .ingest (SURVEY 8f-2, 8f-4) in the default line")
+                    help="--full: skip alternatives.dla_samples / .ingest (SURVEY 8f-2, 8f-4) in a 1-GPU line")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline also measure and check everything else: the CPU baseline, the "
+                         "alternatives (other paths, configs and the widened rows; the --no-* options and "
+                         "--cpu-budget select among them), the panel paths' one-stream GEMM rate and the "
+                         "calc_cddf.py:246 invariant of the outputs.  Without it a run sets up, warms up, times "
+                         "--steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs as DIR/<name>.npy (float64; "
+                         "see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.plan_only or args.workload == "e2e"):
+        ap.error("--dump-outputs needs the timed steps of a c2..c5 workload: not with --plan-only or --workload e2e "
+                 "(whose output is the processed_qsos file under --e2e-dir)")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
         # no launcher: start the N ranks as children (nothing has touched the GPU yet)
@@ -1137,7 +1206,7 @@ def main():
             wl[key] = getattr(args, key)
     if args.plan_only:
         plan_only(wl, world, rank, local_rank, dist if world > 1 else None, args.plan_devices, args.rehearsal,
-                  alternatives=(world > 1 and not args.no_alt and not wl["dr12q"] and wl["k"] == 20
+                  alternatives=(world > 1 and args.full and not args.no_alt and not wl["dr12q"] and wl["k"] == 20
                                 and args.path == "auto"))
         if world > 1:
             with _stdout_to_stderr():
@@ -1165,7 +1234,7 @@ def main():
     packed = syn.pack_spectra(spectra)
     # CPU baseline first, while no process has touched the GPU (its workers are spawned)
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_budget > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_budget > 0:
         cpu = cpu_baseline(model, samples, spectra, args.cpu_budget, args.k,
                            widened=not args.no_alt and not args.no_widened and not wl["dr12q"] and args.k == 20)
     # one GPU per local rank; fewer devices than ranks is refused unless --rehearsal (ranks share devices)
@@ -1216,10 +1285,11 @@ def main():
     local = []
     elapsed = timed_steps(step, eng.synchronize, args.steps, dist if world > 1 else None, local)
     st = eng.stats()
+    dumped = dump_outputs(args.dump_outputs, o_null, o_dla, o_s, o_n, rank, world) if args.dump_outputs else None
     npix = o_n.numpy()
     n_mean = float(np.mean(npix))
     alone = None
-    if path.startswith("panel-GEMM") and args.panel_streams > 1:
+    if args.full and path.startswith("panel-GEMM") and args.panel_streams > 1:
         st1 = single_stream_stats(eng, step, args.panel_streams)
         alone = (i8_roofline(st1, n_mean, args.k, Q, S, 2, path) if path.startswith("panel-GEMM-int8")
                  else f64_gemm_roofline(st1, n_mean, args.k, Q, S, 2))
@@ -1241,7 +1311,7 @@ def main():
     # alternative paths / configs on the same GPU (1 GPU, configs[1] default line).  None is `value`:
     # the headline stays on configs[1] on the path that computes the contraction in fp64.
     alt = None
-    if world == 1 and not args.no_alt and not wl["dr12q"] and args.k == 20 and args.path == "auto":
+    if args.full and world == 1 and not args.no_alt and not wl["dr12q"] and args.k == 20 and args.path == "auto":
         o_s2 = L.DeviceArray(dev, (Q, S), np.float64)
         o_null2, o_dla2 = L.DeviceArray(dev, Q, np.float64), L.DeviceArray(dev, Q, np.float64)
         with Engine(model, samples, set_parameters(k=args.k), device=dev, path="fused_i8") as e2:
@@ -1281,12 +1351,12 @@ def main():
             alt["objective"] = objective_alternative(dev)
 
     # sanity: finite outputs and the calc_cddf.py:246 normalisation invariant on every spectrum
-    inv = invariant_all_rows(o_s, o_dla, S)
-    ok = bool(inv["finite"] and inv["max_abs_dev"] < 1e-10)
+    inv = invariant_all_rows(o_s, o_dla, S) if args.full else None
+    ok = bool(inv["finite"] and inv["max_abs_dev"] < 1e-10) if args.full else None
     for a in (*t.values(), o_null, o_dla, o_s, o_n):
         a.free()
 
-    if world > 1 and not args.no_alt and not wl["dr12q"] and args.k == 20 and args.path == "auto":
+    if args.full and world > 1 and not args.no_alt and not wl["dr12q"] and args.k == 20 and args.path == "auto":
         # the north-star configs at N ranks: configs[3] = the full DR12Q count split
         # over the ranks, and configs[2] end to end on files with every rank writing its own chunks
         alt = {}
@@ -1364,9 +1434,11 @@ def main():
                                          "each panel once per 64 samples (see dram)."},
         "kernel_ms": {"prep": st["prep_ms"] / max(st["prep_launches"], 1), "likelihood": avg_ms,
                       "reduce": st["reduce_ms"] / max(st["reduce_launches"], 1)},
-        "invariant_calc_cddf_246": inv,
-        "checks_ok": ok,
     }
+    if args.full:
+        result.update({"invariant_calc_cddf_246": inv, "checks_ok": ok})
+    if dumped is not None:
+        result["dumped_outputs"] = {"dir": str(args.dump_outputs), "arrays": dumped}
     if rehearsal:
         result["rehearsal"] = {"value_if_counted": value, "distinct_devices": distinct,
                                "note": f"--rehearsal: {world} ranks shared {distinct} GPU(s); not a {world}-GPU point"}

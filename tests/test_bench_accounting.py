@@ -117,3 +117,86 @@ def test_objective_flops_accounting(bench):
     """The objective leg's algorithmic flops: per valid pixel 3k^2 + 12k, per spectrum k^3."""
     y = np.array([[1.0, np.nan, 2.0], [np.nan, np.nan, 3.0]])
     assert bench.objective_flops(y, 4) == 2 * (3 * 16 + 48) + 64 + 1 * (3 * 16 + 48) + 64
+
+
+class _HostArray:
+    """Stands in for _lib.DeviceArray in dump_outputs: shape and numpy(rows, start)."""
+
+    def __init__(self, a):
+        self.a, self.shape = a, a.shape
+
+    def numpy(self, rows=None, start=0):
+        return self.a[start:] if rows is None else self.a[start:start + rows]
+
+
+def test_dump_outputs_writes_a_fixed_sample(bench, tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files under the names Engine.process returns; the Q x S array as a
+    sample that depends on the shape alone (the same entries from run to run), within the byte cap."""
+    rng = np.random.default_rng(2)
+    Q, S = 37, 5000
+    sll = rng.standard_normal((Q, S))
+    arrs = [_HostArray(a) for a in (rng.standard_normal(Q), rng.standard_normal(Q), sll,
+                                    rng.integers(1, 900, Q).astype(np.int32))]
+    shapes = bench.dump_outputs(tmp_path / "a", *arrs)
+    bench.dump_outputs(tmp_path / "b", *arrs)
+    names = {"log_likelihoods_no_dla", "log_likelihoods_dla", "num_pixels", "sample_log_likelihoods_dla"}
+    assert set(shapes) == names and {f.stem for f in (tmp_path / "a").glob("*.npy")} == names
+    for n in names:
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype == np.float64 and list(a.shape) == shapes[n] and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "log_likelihoods_no_dla.npy"), arrs[0].a)
+    assert np.array_equal(np.load(tmp_path / "a" / "num_pixels.npy"), arrs[3].a)
+    got = np.load(tmp_path / "a" / "sample_log_likelihoods_dla.npy")
+    assert got.shape == (Q, bench.DUMP_SAMPLE_COLUMNS)
+    cols = np.sort(np.random.default_rng(0).choice(S, size=bench.DUMP_SAMPLE_COLUMNS, replace=False))
+    assert np.array_equal(got, sll[:, cols])
+    # a cap too small for every row: rows are sampled too, and the file stays under it
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", 10 * 8 * bench.DUMP_SAMPLE_COLUMNS)
+    shapes = bench.dump_outputs(tmp_path / "c", *arrs, rank=1)
+    assert shapes["sample_log_likelihoods_dla"] == [10, bench.DUMP_SAMPLE_COLUMNS]
+    small = np.load(tmp_path / "c" / "sample_log_likelihoods_dla.rank1.npy")
+    assert small.nbytes <= bench.DUMP_SAMPLE_BYTES and all(any(np.array_equal(r, g) for g in got) for r in small)
+    monkeypatch.undo()
+    assert bench.DUMP_SAMPLE_BYTES < bench.DUMP_TOTAL_BYTES <= 64e6
+
+
+def _files_bytes(d):
+    return sum(f.stat().st_size for f in d.glob("*.npy"))
+
+
+def test_dump_outputs_total_stays_under_the_cap(bench, tmp_path, monkeypatch):
+    """The files of a run together stay within DUMP_TOTAL_BYTES (64 MB at the most) whatever the spectrum
+    count: the caps are scaled down here so that small arrays reach every branch, the full-length vectors
+    being sampled once they alone would not fit, and each of N ranks getting 1/N of the caps."""
+    assert bench.DUMP_TOTAL_BYTES <= 64e6
+    monkeypatch.setattr(bench, "DUMP_TOTAL_BYTES", 64_000)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", 48 << 10)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_COLUMNS", 64)
+    rng = np.random.default_rng(3)
+    vmax = (64_000 - (48 << 10) - 4 * bench.NPY_HEADER_BYTES) // 24
+    for Q in (50, vmax, vmax + 1, 5000):
+        arrs = [_HostArray(a) for a in (rng.standard_normal(Q), rng.standard_normal(Q), rng.standard_normal((Q, 100)),
+                                        rng.integers(1, 900, Q).astype(np.int32))]
+        d = tmp_path / f"q{Q}"
+        shapes = bench.dump_outputs(d, *arrs)
+        assert _files_bytes(d) <= 64_000
+        assert shapes["log_likelihoods_dla"] == [min(Q, vmax)]
+        got = np.load(d / "log_likelihoods_dla.npy")
+        assert np.all(np.isin(got, arrs[1].a)) and (Q > vmax or np.array_equal(got, arrs[1].a))
+    # two ranks: each within half the caps, so the run within the whole
+    for r in (0, 1):
+        bench.dump_outputs(tmp_path / "w2", *arrs, rank=r, world=2)
+    assert len(list((tmp_path / "w2").glob("*.npy"))) == 8 and _files_bytes(tmp_path / "w2") <= 64_000
+    # a header size the cap does not allow for is an error, not a silent overrun
+    monkeypatch.setattr(bench, "NPY_HEADER_BYTES", -2000)
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(tmp_path / "over", *arrs)
+
+
+def test_dump_outputs_refused_where_no_timed_step_runs():
+    import subprocess
+    import sys
+    for extra in (["--plan-only"], ["--workload", "e2e"]):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--dump-outputs", "x", *extra],
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "--dump-outputs" in r.stderr

@@ -89,7 +89,7 @@ def _run_bench(*argv, env=None, timeout=240):
 def test_launcher_starts_n_ranks(workload, total):
     """bench.py --gpus 2 with no launcher starts 2 ranks itself (torch.distributed.run children, gloo),
     and rank 0's single JSON line reports both ranks, their devices and disjoint spectrum shards."""
-    r = _run_bench("--gpus", "2", "--plan-only", "--workload", workload)
+    r = _run_bench("--gpus", "2", "--plan-only", "--full", "--workload", workload)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout

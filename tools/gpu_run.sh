@@ -10,7 +10,7 @@
 #   testfile=<path>              one test file (-m gpu)
 #   smoke                        __graft_entry__.smoke()
 #   py=<script>[=<args>]         python <script> <args>            -> <script name>.log
-#   bench=<name>[=<args>]        python bench.py <args>            -> <name>.json
+#   bench=<name>[=<args>]        python bench.py <args>            -> <name>.json  (args --full: CPU baseline, alternatives, checks_ok)
 #   dist=<N>=<name>[=<args>]     torchrun, N ranks sharing the leased GPU -> <name>.json
 #   prof=<name>[=<args>]         tools/profile.sh <tag>_<name> <args> (trace, FETCH, WRITE, SQ)
 #   stall=<name>[=<args>]        tools/profile_stalls.sh <tag>_<name> <args> (issue / wait / MFMA-busy counters)
@@ -78,7 +78,7 @@ for step in "$@"; do
       for r in $(seq 1 "$a"); do
         for v in ${b//,/ }; do
           if [ "$v" = head ]; then L=""; else L=$PWD/tools/variants/$v.so; fi
-          GPDLA_LIB=$L run 600 "$O/ab_${v}_$r.json" python bench.py --cpu-budget 0 --no-alt ${c:-}
+          GPDLA_LIB=$L run 600 "$O/ab_${v}_$r.json" python bench.py --full --cpu-budget 0 --no-alt ${c:-}
           echo -n "$v $r"; summ "$O/ab_${v}_$r.json"
         done
       done ;;
