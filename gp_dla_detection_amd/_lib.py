@@ -75,6 +75,26 @@ class Stats(C.Structure):
                 ("contraction_ms", C.c_double), ("contraction_launches", C.c_int64)]
 
 
+MAX_DLAS = 4
+
+
+class MultiDla(C.Structure):
+    _fields_ = [("max_dlas", C.c_int32), ("min_z_separation", C.c_double), ("occam_log_penalty", C.c_double),
+                ("resample_uniforms", dp), ("forced_base_inds", i32p)]
+
+
+class ResultsMulti(C.Structure):
+    _fields_ = [("memory", C.c_int32), ("log_likelihoods_no_dla", dp), ("log_likelihoods_dla", dp),
+                ("sample_log_likelihoods_dla", dp), ("sample_ld", C.c_int64), ("base_sample_inds", i32p),
+                ("min_z_dlas", dp), ("max_z_dlas", dp), ("num_pixels", i32p)]
+
+
+class MultiStats(C.Structure):
+    _fields_ = [("level_ms", C.c_double * MAX_DLAS), ("level_launches", C.c_int64 * MAX_DLAS),
+                ("resample_ms", C.c_double), ("resample_launches", C.c_int64),
+                ("multi_reduce_ms", C.c_double), ("multi_reduce_launches", C.c_int64)]
+
+
 class DlaPrior(C.Structure):
     _fields_ = [("alpha", C.c_double), ("uniform_min", C.c_double), ("uniform_max", C.c_double),
                 ("fit_min", C.c_double), ("fit_max", C.c_double), ("fit_upper", C.c_double)]
@@ -99,6 +119,10 @@ SIGNATURES = {
     "gpdla_engine_get_stats_n": (C.c_int, [C.c_void_p, C.POINTER(Stats), C.c_int64]),
     "gpdla_engine_reset_stats": (C.c_int, [C.c_void_p]),
     "gpdla_engine_destroy": (None, [C.c_void_p]),
+    "gpdla_engine_process_multi": (C.c_int, [C.c_void_p, C.POINTER(Spectra), C.POINTER(MultiDla),
+                                             C.POINTER(ResultsMulti)]),
+    "gpdla_engine_get_multi_stats": (C.c_int, [C.c_void_p, C.POINTER(MultiStats)]),
+    "gpdla_resample_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, i32p]),
     "gpdla_voigt_f64": (C.c_int, [dp, C.c_int64, C.c_double, C.c_double, C.c_int32, dp]),
     "gpdla_voigt_batch_f64": (C.c_int, [dp, C.c_int64, dp, dp, C.c_int64, C.c_int32, dp]),
     "gpdla_log_mvnpdf_low_rank_f64": (C.c_int, [dp, dp, dp, dp, C.c_int64, C.c_int32, dp]),

@@ -96,7 +96,9 @@ int grow(T** p, size_t* cap, size_t count) {
 
 struct TimedLaunch {
   hipEvent_t start, stop;
-  int kind;  // 0 prep, 1 likelihood, 2 reduce, 3 contraction (panel-GEMM paths, inside 1)
+  int kind;  // 0 prep, 1 likelihood, 2 reduce, 3 contraction (panel-GEMM paths, inside 1);
+             // gpdla_engine_process_multi only: 4 resample, 5 level >= 2 sweep, 6 its log-mean-exp
+  int level; // multi-DLA level the span also counts for in gpdla_multi_stats (0: none)
 };
 
 // One of the two staging sets of the host-buffer pipeline (gpdla_engine_process with host inputs
@@ -184,6 +186,17 @@ struct gpdla_engine {
   hipEvent_t meta_done = nullptr;
 
 
+  // multi-DLA (gpdla_engine_process_multi): the samples in the caller's order, per-batch level
+  // workspaces ([D][nq][S] sample rows, [D][nq] evidences, [D-1][nq][S] base indices, two chain tables
+  // [nq][S][kMaxChain]), the uniforms and forced indices of a call, the resampler's global prefix sums
+  double *d_off_c = nullptr, *d_nhi_c = nullptr;
+  double *d_m_sll = nullptr, *d_m_lldla = nullptr, *d_m_null = nullptr, *d_m_zmin = nullptr, *d_m_zmax = nullptr;
+  double *d_m_u = nullptr, *d_m_cws = nullptr;
+  int32_t *d_m_npix = nullptr, *d_m_base = nullptr, *d_m_chain[2] = {nullptr, nullptr}, *d_m_forced = nullptr;
+  size_t cap_m_sll = 0, cap_m_lldla = 0, cap_m_q[4] = {0, 0, 0, 0}, cap_m_u = 0, cap_m_cws = 0, cap_m_base = 0,
+         cap_m_chain[2] = {0, 0}, cap_m_forced = 0;
+  gpdla_multi_stats mstats{};
+
   std::vector<TimedLaunch> pending;
   gpdla_stats stats{};
 };
@@ -207,6 +220,12 @@ int resolve_events(gpdla_engine* e) {
     if (t.kind == 1) { e->stats.likelihood_ms += ms; e->stats.likelihood_launches++; }
     if (t.kind == 2) { e->stats.reduce_ms += ms; e->stats.reduce_launches++; }
     if (t.kind == 3) { e->stats.contraction_ms += ms; e->stats.contraction_launches++; }
+    if (t.kind == 4) { e->mstats.resample_ms += ms; e->mstats.resample_launches++; }
+    if (t.kind == 6) { e->mstats.multi_reduce_ms += ms; e->mstats.multi_reduce_launches++; }
+    if (t.level >= 1 && t.level <= GPDLA_MAX_DLAS) {
+      e->mstats.level_ms[t.level - 1] += ms;
+      e->mstats.level_launches[t.level - 1]++;
+    }
     (void)hipEventDestroy(t.start);
     (void)hipEventDestroy(t.stop);
   }
@@ -303,7 +322,9 @@ void gpdla_engine_destroy(gpdla_engine* e) {
                   e->d_info, e->d_panel, e->d_lam, e->d_smap, e->d_scratch, e->d_sll,
                   e->d_llnull, e->d_lldla, e->d_zmin, e->d_zmax, e->d_npix, e->d_pm, e->d_srow,
                   e->d_wg, e->d_wu, e->d_G, e->d_U, e->d_q1p, e->d_ldp, e->d_pi8, e->d_psc,
-                  e->d_pent, e->d_ai8};
+                  e->d_pent, e->d_ai8, e->d_off_c, e->d_nhi_c, e->d_m_sll, e->d_m_lldla, e->d_m_null,
+                  e->d_m_zmin, e->d_m_zmax, e->d_m_u, e->d_m_cws, e->d_m_npix, e->d_m_base,
+                  e->d_m_chain[0], e->d_m_chain[1], e->d_m_forced};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (e->h_meta) (void)hipHostFree(e->h_meta);
@@ -981,7 +1002,226 @@ int gpdla_engine_reset_stats(gpdla_engine* e) {
   int rc = resolve_events(e);
   if (rc) return rc;
   e->stats = gpdla_stats{};
+  e->mstats = gpdla_multi_stats{};
   return GPDLA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// multi-DLA search (include/gpdla.h "Multi-DLA search"; kernels in multi_dla.hip)
+// ---------------------------------------------------------------------------------------------
+int gpdla_engine_get_multi_stats(gpdla_engine* e, gpdla_multi_stats* s) {
+  if (!e || !s) return set_error(GPDLA_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  int rc = resolve_events(e);
+  if (rc) return rc;
+  *s = e->mstats;
+  return GPDLA_OK;
+}
+
+// the samples in the caller's order (the engine keeps them in ascending-offset order, d_perm)
+static int multi_caller_samples(gpdla_engine* e) {
+  if (e->d_off_c) return GPDLA_OK;
+  const size_t S = (size_t)e->S;
+  std::vector<double> off(S), nhi(S), off_c(S), nhi_c(S);
+  std::vector<int32_t> perm(S);
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(off.data(), e->d_off, S * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(nhi.data(), e->d_nhi, S * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(perm.data(), e->d_perm, S * 4, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < S; ++i) {
+    off_c[perm[i]] = off[i];
+    nhi_c[perm[i]] = nhi[i];
+  }
+  size_t dummy = 0;
+  int rc;
+  if ((rc = grow(&e->d_nhi_c, &dummy, S))) return rc;
+  HIP_TRY(hipMemcpy(e->d_nhi_c, nhi_c.data(), S * 8, hipMemcpyHostToDevice));
+  dummy = 0;
+  if ((rc = grow(&e->d_off_c, &dummy, S))) return rc;
+  HIP_TRY(hipMemcpy(e->d_off_c, off_c.data(), S * 8, hipMemcpyHostToDevice));
+  return GPDLA_OK;
+}
+
+int gpdla_engine_process_multi(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
+                               const gpdla_results_multi* res) {
+  if (!e || !sp || !mu || !res) return set_error(GPDLA_EINVAL, "null argument");
+  const int D = mu->max_dlas;
+  if (D < 1 || D > GPDLA_MAX_DLAS) return set_error(GPDLA_EINVAL, "max_dlas=%d outside 1..%d", D, GPDLA_MAX_DLAS);
+  if (D > 1 && (e->gemm || e->i8))
+    return set_error(GPDLA_EUNSUPPORTED, "max_dlas=%d needs the fused fp64 path (this engine runs a panel-GEMM or int8 path)", D);
+  if (D > 1 && (e->params.num_lines != 3 || !multi_level_supported(e->K)))
+    return set_error(GPDLA_EUNSUPPORTED, "max_dlas=%d needs num_lines=3 (num_lines=%d)", D, e->params.num_lines);
+  const int64_t Q = sp->num_spectra, S = e->S;
+  if (Q < 0) return set_error(GPDLA_EINVAL, "num_spectra < 0");
+  if (D > 1 && !(mu->min_z_separation >= 0.0) ) return set_error(GPDLA_EINVAL, "min_z_separation must be >= 0");
+  if (D > 1 && !std::isfinite(mu->occam_log_penalty)) return set_error(GPDLA_EINVAL, "occam_log_penalty not finite");
+  if (D > 1 && !mu->resample_uniforms && !mu->forced_base_inds)
+    return set_error(GPDLA_EINVAL, "max_dlas=%d needs resample_uniforms or forced_base_inds", D);
+  if (D > 1 && mu->resample_uniforms)
+    for (int64_t i = 0; i < (D - 1) * S; ++i)
+      if (!(mu->resample_uniforms[i] >= 0.0 && mu->resample_uniforms[i] < 1.0))
+        return set_error(GPDLA_EINVAL, "resample_uniforms[%lld] = %g outside [0, 1)", (long long)i, mu->resample_uniforms[i]);
+  if (D > 1 && mu->forced_base_inds)
+    for (int64_t i = 0; i < (D - 1) * Q * S; ++i)
+      if (mu->forced_base_inds[i] < -1 || mu->forced_base_inds[i] >= S)
+        return set_error(GPDLA_EINVAL, "forced_base_inds[%lld] = %d outside -1..%lld", (long long)i,
+                         (int)mu->forced_base_inds[i], (long long)(S - 1));
+  if (Q == 0) return GPDLA_OK;
+  if (!sp->offsets || !sp->z_qsos) return set_error(GPDLA_EINVAL, "null spectra array");
+  if (!res->log_likelihoods_no_dla || !res->log_likelihoods_dla) return set_error(GPDLA_EINVAL, "null result array");
+  if ((res->sample_log_likelihoods_dla || res->base_sample_inds) && res->sample_ld < S)
+    return set_error(GPDLA_EINVAL, "sample_ld (%lld) < num_samples (%lld)", (long long)res->sample_ld, (long long)S);
+  HIP_TRY(hipSetDevice(e->device));
+  int rc;
+  if (D > 1 && (rc = multi_caller_samples(e))) return rc;
+  hipStream_t st = e->stream;
+  const bool out_dev = res->memory == GPDLA_MEM_DEVICE;
+  const hipMemcpyKind out_kind = out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const bool forced = D > 1 && mu->forced_base_inds;
+  // the batch of gpdla_engine_process: one call of it below is exactly one of its device batches,
+  // whose panel, padded wavelengths and spectrum infos then stay in the engine for the deeper levels
+  const int64_t QB = e->params.max_batch_spectra > 0 ? e->params.max_batch_spectra : (e->gemm ? 64 : 1024);
+  if (D > 1 && mu->resample_uniforms) {
+    if ((rc = grow(&e->d_m_u, &e->cap_m_u, (size_t)((D - 1) * S)))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_m_u, mu->resample_uniforms, (size_t)(D - 1) * S * 8, hipMemcpyHostToDevice, st));
+  }
+  for (int64_t q0 = 0; q0 < Q; q0 += QB) {
+    const int64_t nq = std::min(QB, Q - q0);
+    const size_t plane = (size_t)nq * S;
+    if ((rc = grow(&e->d_m_sll, &e->cap_m_sll, plane * D))) return rc;
+    if ((rc = grow(&e->d_m_lldla, &e->cap_m_lldla, (size_t)nq * D))) return rc;
+    if ((rc = grow(&e->d_m_null, &e->cap_m_q[0], (size_t)nq))) return rc;
+    if ((rc = grow(&e->d_m_zmin, &e->cap_m_q[1], (size_t)nq))) return rc;
+    if ((rc = grow(&e->d_m_zmax, &e->cap_m_q[2], (size_t)nq))) return rc;
+    if ((rc = grow(&e->d_m_npix, &e->cap_m_q[3], (size_t)nq))) return rc;
+    if (D > 1) {
+      if ((rc = grow(&e->d_m_base, &e->cap_m_base, plane * (D - 1)))) return rc;
+      for (int i = 0; i < 2; ++i)
+        if ((rc = grow(&e->d_m_chain[i], &e->cap_m_chain[i], plane * kMaxChain))) return rc;
+      if (S > GPDLA_RESAMPLE_LDS && !forced && (rc = grow(&e->d_m_cws, &e->cap_m_cws, plane))) return rc;
+      if (forced) {
+        if ((rc = grow(&e->d_m_forced, &e->cap_m_forced, plane * (D - 1)))) return rc;
+        for (int d = 2; d <= D; ++d)
+          HIP_TRY(hipMemcpyAsync(e->d_m_forced + (size_t)(d - 2) * plane,
+                                 mu->forced_base_inds + ((int64_t)(d - 2) * Q + q0) * S, plane * 4,
+                                 hipMemcpyHostToDevice, st));
+      }
+    }
+    // level 1: the single-DLA engine itself, into the level workspaces
+    gpdla_spectra sub = *sp;
+    sub.num_spectra = nq;
+    sub.offsets = sp->offsets + q0;
+    sub.z_qsos = sp->z_qsos + q0;
+    gpdla_results r1{};
+    r1.memory = GPDLA_MEM_DEVICE;
+    r1.log_likelihoods_no_dla = e->d_m_null;
+    r1.sample_log_likelihoods_dla = e->d_m_sll;
+    r1.sample_ld = S;
+    r1.log_likelihoods_dla = e->d_m_lldla;
+    r1.min_z_dlas = e->d_m_zmin; r1.max_z_dlas = e->d_m_zmax; r1.num_pixels = e->d_m_npix;
+    const size_t p0 = e->pending.size();
+    if ((rc = gpdla_engine_process(e, &sub, &r1)) < 0) return rc;
+    for (size_t i = p0; i < e->pending.size(); ++i)
+      if (e->pending[i].kind == 1) e->pending[i].level = 1;
+
+    for (int d = 2; d <= D; ++d) {
+      int32_t* chain_prev = e->d_m_chain[d & 1];        // built at level d - 1 (unused at d = 2)
+      int32_t* chain_next = e->d_m_chain[(d + 1) & 1];
+      ResampleArgs ra{};
+      ra.rows = (int32_t)nq; ra.ll = e->d_m_sll + (size_t)(d - 2) * plane; ra.ld = S; ra.S = S;
+      ra.u = forced ? nullptr : e->d_m_u + (size_t)(d - 2) * S;
+      ra.forced = forced ? e->d_m_forced + (size_t)(d - 2) * plane : nullptr;
+      ra.cws = e->d_m_cws;
+      ra.chain_prev = chain_prev; ra.prev_len = d - 2; ra.chain_next = chain_next;
+      ra.base_inds = e->d_m_base + (size_t)(d - 2) * plane;
+      TimedLaunch t4{}, t5{}, t6{};
+      if ((rc = record_start(e, &t4, 4))) return rc;
+      HIP_TRY(launch_resample(ra, st));
+      HIP_TRY(hipEventRecord(t4.stop, st));
+      e->pending.push_back(t4);
+
+      MultiLevelArgs la{};
+      la.q_count = (int32_t)nq; la.info = e->d_info; la.panel = e->d_panel; la.lam_pad = e->d_lam;
+      la.offsets = e->d_off; la.nhi = e->d_nhi; la.perm = e->d_perm;
+      la.offsets_c = e->d_off_c; la.nhi_c = e->d_nhi_c;
+      la.chain = chain_next; la.chain_len = d - 1; la.S = S;
+      la.lines = make_line_args(e->d_lines);
+      la.min_z_separation = mu->min_z_separation;
+      la.sample_ll = e->d_m_sll + (size_t)(d - 1) * plane; la.ld = S; la.status = e->d_status;
+      if ((rc = record_start(e, &t5, 5))) return rc;
+      t5.level = d;
+      HIP_TRY(launch_multi_level(e->K, la, st));
+      HIP_TRY(hipEventRecord(t5.stop, st));
+      e->pending.push_back(t5);
+
+      MultiReduceArgs ma{};
+      ma.q_count = (int32_t)nq; ma.sample_ll = la.sample_ll; ma.ld = S; ma.S = S;
+      ma.penalty = (d - 1) * mu->occam_log_penalty;
+      ma.ll_dla = e->d_m_lldla + (size_t)(d - 1) * nq;
+      if ((rc = record_start(e, &t6, 6))) return rc;
+      HIP_TRY(launch_multi_reduce(ma, st));
+      HIP_TRY(hipEventRecord(t6.stop, st));
+      e->pending.push_back(t6);
+    }
+
+    HIP_TRY(hipMemcpyAsync(res->log_likelihoods_no_dla + q0, e->d_m_null, nq * 8, out_kind, st));
+    if (res->min_z_dlas) HIP_TRY(hipMemcpyAsync(res->min_z_dlas + q0, e->d_m_zmin, nq * 8, out_kind, st));
+    if (res->max_z_dlas) HIP_TRY(hipMemcpyAsync(res->max_z_dlas + q0, e->d_m_zmax, nq * 8, out_kind, st));
+    if (res->num_pixels) HIP_TRY(hipMemcpyAsync(res->num_pixels + q0, e->d_m_npix, nq * 4, out_kind, st));
+    for (int d = 1; d <= D; ++d) {
+      HIP_TRY(hipMemcpyAsync(res->log_likelihoods_dla + (int64_t)(d - 1) * Q + q0, e->d_m_lldla + (size_t)(d - 1) * nq,
+                             nq * 8, out_kind, st));
+      if (res->sample_log_likelihoods_dla)
+        HIP_TRY(hipMemcpy2DAsync(res->sample_log_likelihoods_dla + ((int64_t)(d - 1) * Q + q0) * res->sample_ld,
+                                 res->sample_ld * 8, e->d_m_sll + (size_t)(d - 1) * plane, S * 8, S * 8, nq, out_kind, st));
+      if (res->base_sample_inds && d >= 2)
+        HIP_TRY(hipMemcpy2DAsync(res->base_sample_inds + ((int64_t)(d - 2) * Q + q0) * res->sample_ld,
+                                 res->sample_ld * 4, e->d_m_base + (size_t)(d - 2) * plane, S * 4, S * 4, nq, out_kind, st));
+    }
+    // the level workspaces are reused by the next batch: drain
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  return gpdla_engine_synchronize(e);
+}
+
+int gpdla_resample_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld, const double* u,
+                       int32_t* out_inds) {
+  if (!ll || !u || !out_inds) return set_error(GPDLA_EINVAL, "null argument");
+  if (rows < 0 || S < 1 || ld < S || rows > INT32_MAX || S > INT32_MAX)
+    return set_error(GPDLA_EINVAL, "rows=%lld S=%lld ld=%lld", (long long)rows, (long long)S, (long long)ld);
+  for (int64_t j = 0; j < S; ++j)
+    if (!(u[j] >= 0.0 && u[j] < 1.0)) return set_error(GPDLA_EINVAL, "u[%lld] = %g outside [0, 1)", (long long)j, u[j]);
+  int rc = check_device(device);
+  if (rc) return rc;
+  if (rows == 0) return GPDLA_OK;
+  HIP_TRY(hipSetDevice(device));
+  double *d_ll = nullptr, *d_u = nullptr, *d_c = nullptr;
+  int32_t* d_b = nullptr;
+  auto done = [&](int code) {
+    for (void* p : {(void*)d_ll, (void*)d_u, (void*)d_c, (void*)d_b})
+      if (p) (void)hipFree(p);
+    return code;
+  };
+#define TRY_R(expr)                                                                                         \
+  do {                                                                                                      \
+    hipError_t e_ = (expr);                                                                                 \
+    if (e_ != hipSuccess)                                                                                   \
+      return done(set_error(e_ == hipErrorOutOfMemory ? GPDLA_ENOMEM : GPDLA_EDEVICE, "resample: %s failed: %s", \
+                            #expr, hipGetErrorString(e_)));                                                 \
+  } while (0)
+  TRY_R(hipMalloc((void**)&d_ll, (size_t)rows * ld * 8));
+  TRY_R(hipMalloc((void**)&d_u, (size_t)S * 8));
+  TRY_R(hipMalloc((void**)&d_b, (size_t)rows * S * 4));
+  if (S > GPDLA_RESAMPLE_LDS) TRY_R(hipMalloc((void**)&d_c, (size_t)rows * S * 8));
+  TRY_R(hipMemcpy(d_ll, ll, (size_t)rows * ld * 8, hipMemcpyHostToDevice));
+  TRY_R(hipMemcpy(d_u, u, (size_t)S * 8, hipMemcpyHostToDevice));
+  ResampleArgs ra{};
+  ra.rows = (int32_t)rows; ra.ll = d_ll; ra.ld = ld; ra.S = S; ra.u = d_u; ra.cws = d_c; ra.base_inds = d_b;
+  TRY_R(launch_resample(ra, nullptr));
+  TRY_R(hipMemcpy(out_inds, d_b, (size_t)rows * S * 4, hipMemcpyDeviceToHost));
+#undef TRY_R
+  return done(GPDLA_OK);
 }
 
 // ---------------------------------------------------------------------------------------------

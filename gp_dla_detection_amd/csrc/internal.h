@@ -453,6 +453,62 @@ int panel_row_doubles(int K);
 int panel_lds_row_doubles(int K);
 int scratch_doubles(int K);
 
+// ---- multi-DLA levels (multi_dla.hip; fused fp64 layout, num_lines = 3)
+constexpr int kMaxDlas = 4;
+constexpr int kMaxChain = kMaxDlas - 1;   // base DLAs a sample can carry
+
+// Level d = 1 + chain_len: sample j (caller order) carries its own DLA and those of the samples
+// chain[(q S + j) kMaxChain + i], i < chain_len (caller-order indices; -1 = no chain: NaN output).
+struct MultiLevelArgs {
+  int32_t q_count;
+  const SpecInfo* info;
+  const double* panel;
+  const double* lam_pad;
+  const double* offsets;         // [S] ascending (the sweep order)
+  const double* nhi;             // [S] in sweep order
+  const int32_t* perm;           // [S] sweep index -> caller's sample index
+  const double* offsets_c;       // [S] caller order
+  const double* nhi_c;           // [S] caller order
+  const int32_t* chain;          // [q_count][S][kMaxChain]
+  int32_t chain_len;             // d - 1
+  int64_t S;
+  LineArgs lines;
+  double min_z_separation;
+  double* sample_ll;             // [q_count][ld]
+  int64_t ld;
+  int32_t* status;
+};
+
+// Steps 1-3 of a level (weights, prefix sum, S searches, next chain table), one block per row.
+struct ResampleArgs {
+  int32_t rows;
+  const double* ll;              // [rows][ld] previous level, caller order
+  int64_t ld;
+  int64_t S;
+  const double* u;               // [S] uniforms of this level; unused with forced
+  const int32_t* forced;         // [rows][S] base indices to use instead of resampling, or nullptr
+  double* cws;                   // [rows][S] prefix-sum workspace, read only when S > kResampleLds
+  const int32_t* chain_prev;     // [rows][S][kMaxChain] or nullptr (no chain output)
+  int32_t prev_len;              // entries of chain_prev in use (d - 2)
+  int32_t* chain_next;           // [rows][S][kMaxChain] or nullptr
+  int32_t* base_inds;            // [rows][S] out
+};
+
+// NaN-aware log-mean-exp of a level >= 2, minus the Occam penalty
+struct MultiReduceArgs {
+  int32_t q_count;
+  const double* sample_ll;
+  int64_t ld;
+  int64_t S;
+  double penalty;                // (d - 1) occam_log_penalty
+  double* ll_dla;                // [q_count]
+};
+
+bool multi_level_supported(int K);
+hipError_t launch_multi_level(int K, const MultiLevelArgs& a, hipStream_t s);
+hipError_t launch_resample(const ResampleArgs& a, hipStream_t s);
+hipError_t launch_multi_reduce(const MultiReduceArgs& a, hipStream_t s);
+
 // host-side table fitting (faddeeva_host.cpp)
 void fit_core_table(int line, double* core);
 void fit_wing_line(int line, double* wing);

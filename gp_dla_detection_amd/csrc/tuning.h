@@ -21,6 +21,25 @@
 #define GPDLA_MAX_CHUNK 131072
 #endif
 
+// multi_level_kernel (multi_dla.hip): blocks per CU by compiled rank and DLAs per sample.  Not tuned
+// by an A/B: the largest occupancy at which every instantiation compiles without scratch (register
+// report in DESIGN.md "Multi-DLA"); 2 blocks up to this rank, 1 above it.
+#ifndef GPDLA_MULTI_2BLOCK_MAXK_D2
+#define GPDLA_MULTI_2BLOCK_MAXK_D2 16
+#endif
+#ifndef GPDLA_MULTI_2BLOCK_MAXK_D3
+#define GPDLA_MULTI_2BLOCK_MAXK_D3 12
+#endif
+#ifndef GPDLA_MULTI_2BLOCK_MAXK_D4
+#define GPDLA_MULTI_2BLOCK_MAXK_D4 0
+#endif
+
+// resample_kernel (multi_dla.hip): doubles of the prefix sum kept in LDS (128 KiB of the CU's 160);
+// rows with more samples keep it in a global workspace
+#ifndef GPDLA_RESAMPLE_LDS
+#define GPDLA_RESAMPLE_LDS 16384
+#endif
+
 // gemm_i8_bst_kernel: share of an XCD's u sample tiles taken by its two spare blocks (the Gram
 // blocks take the rest after their columns); configs[4]: 0.15 / 0.25 / 0.35 / 0.40 / 0.45 / 0.50 /
 // 0.55 / 0.65 -> 9.96 / 9.97 / 9.99 / 10.08 / 10.03 / 9.79 / 9.44 / 8.93e7 evals/s (profiles/round5/r10h-j)

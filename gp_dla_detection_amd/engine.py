@@ -127,6 +127,115 @@ class Engine:
             L.check(rc)
         return out
 
+    # ------------------------------------------------------------------------------ multi-DLA
+    def default_resample_uniforms(self, max_dlas: int) -> np.ndarray:
+        """The (max_dlas - 1) x S uniforms of the level resamplers when the caller gives none: the
+        RR2-scrambled Halton dimensions after the samples' own bases 2 and 3, from point 1."""
+        from .dla_samples import halton_rr2
+        if max_dlas <= 1:
+            return np.zeros((0, self.num_samples))
+        pts = halton_rr2(self.num_samples, bases=(5, 7, 11)[:max_dlas - 1], start=1, device=self.device)
+        return np.ascontiguousarray(pts.T)
+
+    def process_multi(self, packed: dict, max_dlas: int, resample_uniforms=None, base_sample_inds=None,
+                      want_samples: bool = True, min_z_separation: float | None = None,
+                      occam_log_penalty: float | None = None, raise_numeric: bool = False,
+                      memory: str = "host") -> dict:
+        """The multi-DLA search (gpdla_engine_process_multi): up to ``max_dlas`` (1..4) DLAs per
+        sightline on the fused fp64 path.  Level d's sample j carries its own DLA and those of the base
+        sample drawn for it from the level-(d-1) posterior with ``resample_uniforms[d-2, j]``
+        ((max_dlas - 1) x S in [0, 1); default ``default_resample_uniforms``).  ``base_sample_inds``
+        ((max_dlas - 1) x Q x S, 0-based, -1 = none) replaces the resampler (tests, replaying a saved run).
+        Returns ``log_likelihoods_dla`` (D x Q), ``sample_log_likelihoods_dla`` (D x Q x S),
+        ``base_sample_inds`` ((D - 1) x Q x S int32, -1 = none) and the per-spectrum vectors of
+        ``process``.  ``memory="device"`` routes inputs and results through device buffers (same values)."""
+        D, S = int(max_dlas), self.num_samples
+        offsets = np.ascontiguousarray(packed["offsets"], dtype=np.int64)
+        Q = offsets.size - 1
+        wl = np.ascontiguousarray(packed["wavelengths"], dtype=np.float64)
+        fl = np.ascontiguousarray(packed["flux"], dtype=np.float64)
+        nv = np.ascontiguousarray(packed["noise_variance"], dtype=np.float64)
+        mk = np.ascontiguousarray(packed["pixel_mask"], dtype=np.uint8)
+        zq = np.ascontiguousarray(packed["z_qsos"], dtype=np.float64)
+        if not (wl.size == fl.size == nv.size == mk.size and offsets[-1] <= wl.size and zq.size == Q):
+            raise ValueError("inconsistent spectra arrays")
+        Dc = min(max(D, 1), L.MAX_DLAS)   # array sizes for an out-of-range D (the library rejects it)
+        forced = None
+        if base_sample_inds is not None:
+            forced = np.ascontiguousarray(base_sample_inds, dtype=np.int32)
+            if forced.shape != (Dc - 1, Q, S):
+                raise ValueError(f"base_sample_inds must be {(Dc - 1, Q, S)}")
+        u = None
+        if resample_uniforms is not None:
+            u = np.ascontiguousarray(resample_uniforms, dtype=np.float64)
+            if u.shape != (Dc - 1, S):
+                raise ValueError(f"resample_uniforms must be {(Dc - 1, S)}")
+        elif forced is None and 1 < D <= L.MAX_DLAS:
+            u = self.default_resample_uniforms(D)
+        from .parameters import kms_to_z
+        md = L.MultiDla(max_dlas=D,
+                        min_z_separation=kms_to_z(3000) if min_z_separation is None else float(min_z_separation),
+                        occam_log_penalty=float(np.log(S)) if occam_log_penalty is None else float(occam_log_penalty),
+                        resample_uniforms=L.ptr(u) if u is not None and u.size else None,
+                        forced_base_inds=L.ptr(forced, C.c_int32) if forced is not None and forced.size else None)
+        out = dict(log_likelihoods_no_dla=np.full(Q, np.nan), log_likelihoods_dla=np.full((Dc, Q), np.nan),
+                   min_z_dlas=np.full(Q, np.nan), max_z_dlas=np.full(Q, np.nan),
+                   num_pixels=np.zeros(Q, dtype=np.int32), max_dlas=D)
+        if want_samples:
+            out["sample_log_likelihoods_dla"] = np.full((Dc, Q, S), np.nan)
+            out["base_sample_inds"] = np.full((Dc - 1, Q, S), -1, dtype=np.int32)
+        if memory == "host":
+            sp = L.Spectra(memory=L.MEM_HOST, num_spectra=Q, offsets=L.ptr(offsets, C.c_int64),
+                           wavelengths=L.ptr(wl), flux=L.ptr(fl), noise_variance=L.ptr(nv),
+                           pixel_mask=L.ptr(mk, C.c_uint8), z_qsos=L.ptr(zq))
+            sll, base = out.get("sample_log_likelihoods_dla"), out.get("base_sample_inds")
+            rs = L.ResultsMulti(memory=L.MEM_HOST, log_likelihoods_no_dla=L.ptr(out["log_likelihoods_no_dla"]),
+                                log_likelihoods_dla=L.ptr(out["log_likelihoods_dla"]),
+                                sample_log_likelihoods_dla=L.ptr(sll), sample_ld=S,
+                                base_sample_inds=L.ptr(base, C.c_int32) if base is not None and base.size else None,
+                                min_z_dlas=L.ptr(out["min_z_dlas"]), max_z_dlas=L.ptr(out["max_z_dlas"]),
+                                num_pixels=L.ptr(out["num_pixels"], C.c_int32))
+            rc = self.lib.gpdla_engine_process_multi(self._h, C.byref(sp), C.byref(md), C.byref(rs))
+        elif memory == "device":
+            dev = {k: L.DeviceArray.from_numpy(v, self.device) for k, v in
+                   dict(wl=wl, fl=fl, nv=nv, mk=mk, zq=zq).items()}
+            dout = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in out.items()
+                    if isinstance(v, np.ndarray) and v.size}
+            sp = L.Spectra(memory=L.MEM_DEVICE, num_spectra=Q, offsets=L.ptr(offsets, C.c_int64),
+                           wavelengths=L.dev_ptr(dev["wl"].ptr), flux=L.dev_ptr(dev["fl"].ptr),
+                           noise_variance=L.dev_ptr(dev["nv"].ptr), pixel_mask=L.dev_ptr(dev["mk"].ptr, C.c_uint8),
+                           z_qsos=L.dev_ptr(dev["zq"].ptr))
+
+            def dptr(key, ctype=C.c_double):
+                return L.dev_ptr(dout[key].ptr, ctype) if key in dout else None
+            rs = L.ResultsMulti(memory=L.MEM_DEVICE, log_likelihoods_no_dla=dptr("log_likelihoods_no_dla"),
+                                log_likelihoods_dla=dptr("log_likelihoods_dla"),
+                                sample_log_likelihoods_dla=dptr("sample_log_likelihoods_dla"), sample_ld=S,
+                                base_sample_inds=dptr("base_sample_inds", C.c_int32),
+                                min_z_dlas=dptr("min_z_dlas"), max_z_dlas=dptr("max_z_dlas"),
+                                num_pixels=dptr("num_pixels", C.c_int32))
+            rc = self.lib.gpdla_engine_process_multi(self._h, C.byref(sp), C.byref(md), C.byref(rs))
+            if rc in (L.GPDLA_OK, L.GPDLA_ENUMERIC):
+                for k, d in dout.items():
+                    out[k] = d.numpy()
+            for d in list(dev.values()) + list(dout.values()):
+                d.free()
+        else:
+            raise ValueError("memory must be 'host' or 'device'")
+        if rc == L.GPDLA_ENUMERIC and not raise_numeric:
+            out["numeric_warning"] = self.lib.gpdla_last_error().decode()
+        else:
+            L.check(rc)
+        return out
+
+    def multi_stats(self) -> dict:
+        """gpdla_engine_get_multi_stats: per-level likelihood ms / launches, resample and reduce ms."""
+        s = L.MultiStats()
+        L.check(self.lib.gpdla_engine_get_multi_stats(self._h, C.byref(s)))
+        return dict(level_ms=list(s.level_ms), level_launches=list(s.level_launches),
+                    resample_ms=s.resample_ms, resample_launches=s.resample_launches,
+                    multi_reduce_ms=s.multi_reduce_ms, multi_reduce_launches=s.multi_reduce_launches)
+
     # ------------------------------------------------------------------------- device path
     def process_device(self, offsets: np.ndarray, wl_ptr: int, flux_ptr: int, noise_ptr: int,
                        mask_ptr: int, z_ptr: int, ll_null_ptr: int, ll_dla_ptr: int,
@@ -199,6 +308,20 @@ class Engine:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def resample(log_likelihoods, uniforms, device: int = 0) -> np.ndarray:
+    """The multi-DLA resampler alone (gpdla_resample_f64): for each row of S log likelihoods, the
+    index of the smallest i whose weight prefix sum exceeds ``uniforms[j]`` times the total (weights
+    exp(l - max), NaN -> 0); -1 throughout a row without a finite positive total.  int32, rows x S."""
+    ll = np.ascontiguousarray(np.atleast_2d(log_likelihoods), dtype=np.float64)
+    u = np.ascontiguousarray(uniforms, dtype=np.float64).ravel()
+    rows, S = ll.shape
+    if u.size != S:
+        raise ValueError("one uniform per sample")
+    out = np.empty((rows, S), dtype=np.int32)
+    L.check(L.load().gpdla_resample_f64(device, L.ptr(ll), rows, S, S, L.ptr(u), L.ptr(out, C.c_int32)))
+    return out
 
 
 def voigt(lambdas, z, N, num_lines=31) -> np.ndarray:

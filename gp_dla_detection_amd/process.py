@@ -62,6 +62,36 @@ def model_posteriors(log_posteriors_no_dla, log_posteriors_dla):
     return post, p_no, 1 - p_no
 
 
+def multi_dla_priors(z_qsos, prior_z_qsos, prior_dla_ind, max_dlas: int = 1,
+                     prior_z_qso_increase=P.PRIOR_Z_QSO_INCREASE):
+    """Model priors of the multi-DLA search: with p = M / N of process_qsos.m:123-127, no DLA has prior
+    1 - p, exactly d DLAs p^d - p^(d+1) for d < max_dlas and p^max_dlas for d = max_dlas (they sum to 1).
+    Returns (log_priors_no_dla [Q], log_priors_dla [Q x max_dlas]); for max_dlas = 1 these are
+    ``dla_priors``'s two arrays, bit for bit."""
+    if not 1 <= max_dlas <= 4:
+        raise ValueError("max_dlas must be 1..4")
+    lp_no, lp1 = dla_priors(z_qsos, prior_z_qsos, prior_dla_ind, prior_z_qso_increase)
+    if max_dlas == 1:
+        return lp_no, lp1[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = np.exp(lp1)
+        cols = [np.log(p ** d - p ** (d + 1)) for d in range(1, max_dlas)] + [np.log(p ** max_dlas)]
+    return lp_no, np.stack(cols, axis=1)
+
+
+def model_posteriors_multi(log_posteriors_no_dla, log_posteriors_dla):
+    """process_qsos.m:222-232 over 1 + D models: ``log_posteriors_dla`` is Q x D.  A level d >= 2 whose
+    evidence is NaN (no finite sample below it) enters with posterior 0."""
+    lp_dla = np.array(log_posteriors_dla, dtype=np.float64)
+    lp_dla[:, 1:] = np.where(np.isnan(lp_dla[:, 1:]), -np.inf, lp_dla[:, 1:])
+    lp = np.concatenate([np.asarray(log_posteriors_no_dla, dtype=np.float64)[:, None], lp_dla], axis=1)
+    mx = np.max(lp, axis=1, keepdims=True)
+    post = np.exp(lp - mx)
+    post = post / np.sum(post, axis=1, keepdims=True)
+    p_no = post[:, 0]
+    return post, p_no, 1 - p_no
+
+
 def _select(spectra, test_ind):
     if isinstance(spectra, dict) and "offsets" in spectra:
         packed = spectra
@@ -84,18 +114,62 @@ def _select(spectra, test_ind):
 
 
 def _engine_compute(model: dict, samples: dict, packed: dict, params: Parameters, device: int = 0,
-                    engine: Engine | None = None) -> dict:
-    """The hot path on the GPU: per-spectrum null / sample / DLA log likelihoods and z ranges."""
+                    engine: Engine | None = None, max_dlas: int = 1) -> dict:
+    """The hot path on the GPU: per-spectrum null / sample / DLA log likelihoods and z ranges; with
+    ``max_dlas`` > 1 every level of the multi-DLA search (Engine.process_multi's arrays)."""
     eng = engine or Engine(model, samples, params, device=device)
     try:
+        if max_dlas > 1:
+            return eng.process_multi(packed, max_dlas, want_samples=True)
         return eng.process(packed, want_samples=True)
     finally:
         if engine is None:
             eng.close()
 
 
-def _finish(res: dict, z_qsos, prior: dict | None, params: Parameters, metadata: dict | None) -> dict:
+def _finish_multi(res: dict, z_qsos, prior: dict | None, params: Parameters, metadata: dict | None,
+                  max_dlas: int) -> dict:
+    """``_finish`` for max_dlas > 1, in MATLAB shapes: ``res`` holds Engine.process_multi's arrays
+    (D x Q evidences, D x Q x S sample rows, (D - 1) x Q x S 0-based base indices)."""
+    Q, D = np.asarray(z_qsos).size, int(max_dlas)
+    lld = np.ascontiguousarray(np.asarray(res["log_likelihoods_dla"], dtype=np.float64).T)       # Q x D
+    if lld.shape != (Q, D):
+        raise ValueError(f"log_likelihoods_dla must be {(D, Q)} for max_dlas={D}")
+    out = dict(
+        min_z_dlas=res["min_z_dlas"], max_z_dlas=res["max_z_dlas"],
+        log_likelihoods_no_dla=res["log_likelihoods_no_dla"], log_likelihoods_dla=lld,
+        num_pixels=res["num_pixels"], num_lines=params.num_lines, max_z_cut=params.max_z_cut,
+        prior_z_qso_increase=params.prior_z_qso_increase, max_dlas=D)
+    if "sample_log_likelihoods_dla" in res:                                  # Q x S x D
+        out["sample_log_likelihoods_dla"] = np.ascontiguousarray(
+            np.transpose(np.asarray(res["sample_log_likelihoods_dla"]), (1, 2, 0)))
+    if "base_sample_inds" in res:   # 1-based doubles, 0 = none: Q x S for D = 2, Q x S x (D - 1) beyond
+        b = np.transpose(np.asarray(res["base_sample_inds"]), (1, 2, 0)).astype(np.float64) + 1.0
+        out["base_sample_inds"] = np.ascontiguousarray(b[:, :, 0] if D == 2 else b)
+    if prior is not None:
+        dla_ind = filter_prior_dlas(prior["z_qsos"], prior["dla_ind"], prior.get("z_dlas", [None] * len(prior["z_qsos"])))
+        lp_no, lp_dla = multi_dla_priors(z_qsos, prior["z_qsos"], dla_ind, D, params.prior_z_qso_increase)
+    else:
+        p = 0.5
+        lp_no = np.full(Q, np.log(1 - p))
+        lp_dla = np.tile(np.log([p ** d - p ** (d + 1) for d in range(1, D)] + [p ** D]), (Q, 1))
+    out["log_priors_no_dla"], out["log_priors_dla"] = lp_no, lp_dla
+    out["log_posteriors_no_dla"] = lp_no + out["log_likelihoods_no_dla"]
+    out["log_posteriors_dla"] = lp_dla + lld
+    post, p_no, p_dla = model_posteriors_multi(out["log_posteriors_no_dla"], out["log_posteriors_dla"])
+    out["model_posteriors"], out["p_no_dlas"], out["p_dlas"] = post, p_no, p_dla
+    if "numeric_warning" in res:
+        out["numeric_warning"] = res["numeric_warning"]
+    for key, val in (metadata or {}).items():
+        out[key] = val
+    return out
+
+
+def _finish(res: dict, z_qsos, prior: dict | None, params: Parameters, metadata: dict | None,
+            max_dlas: int = 1) -> dict:
     """process_qsos.m:122-132, 150-155, 202-232: priors, posteriors and the saved scalars."""
+    if max_dlas > 1:
+        return _finish_multi(res, z_qsos, prior, params, metadata, max_dlas)
     Q = np.asarray(z_qsos).size
     out = dict(
         min_z_dlas=res["min_z_dlas"], max_z_dlas=res["max_z_dlas"],
@@ -124,12 +198,22 @@ def _finish(res: dict, z_qsos, prior: dict | None, params: Parameters, metadata:
 
 def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
                  params: Parameters | None = None, test_ind=None, engine: Engine | None = None,
-                 device: int = 0, metadata: dict | None = None) -> dict:
-    """Run the DLA search (process_qsos.m:88-232) and return the saved variables."""
+                 device: int = 0, metadata: dict | None = None, max_dlas: int = 1, compute=None) -> dict:
+    """Run the DLA search (process_qsos.m:88-232) and return the saved variables.  ``max_dlas`` > 1
+    (up to 4) runs the multi-DLA search: ``log_likelihoods_dla`` / ``log_priors_dla`` /
+    ``log_posteriors_dla`` become Q x D, ``model_posteriors`` Q x (1 + D), ``sample_log_likelihoods_dla``
+    Q x S x D, and ``base_sample_inds`` (1-based, 0 = none; Q x S for D = 2, else Q x S x (D - 1)) and
+    ``max_dlas`` are added.  ``compute(model, samples, packed, params, device, max_dlas=D)`` replaces the
+    engine (tests) and returns Engine.process / process_multi's arrays."""
+    if not 1 <= int(max_dlas) <= 4:
+        raise ValueError("max_dlas must be 1..4")
     params = params or set_parameters(k=np.asarray(model["M"]).shape[1])
     packed = _select(spectra, test_ind)
-    res = _engine_compute(model, samples, packed, params, device, engine)
-    out = _finish(res, packed["z_qsos"], prior, params, metadata)
+    if compute is not None:
+        res = compute(model, samples, packed, params, device, **(dict(max_dlas=max_dlas) if max_dlas > 1 else {}))
+    else:
+        res = _engine_compute(model, samples, packed, params, device, engine, max_dlas)
+    out = _finish(res, packed["z_qsos"], prior, params, metadata, max_dlas)
     if test_ind is not None:
         out["test_ind"] = np.asarray(test_ind)
     return out
@@ -142,6 +226,8 @@ PROCESSED_VARIABLES = ("training_release", "training_set_name", "dla_catalog_nam
                        "log_likelihoods_no_dla", "sample_log_likelihoods_dla", "log_likelihoods_dla",
                        "log_posteriors_no_dla", "log_posteriors_dla", "model_posteriors", "p_no_dlas",
                        "p_dlas")
+# what a multi-DLA run (max_dlas > 1) saves besides; calc_cddf.py:112-115,225 reads base_sample_inds
+MULTI_DLA_VARIABLES = ("base_sample_inds", "max_dlas")
 
 
 def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
@@ -152,9 +238,15 @@ def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
     default container is v7.3 (HDF5, matv73.py): what the reference writes and what
     calc_cddf.py reads with h5py (Q-vectors as (1, Q), the sample array as (S, Q)); it has no
     per-variable size limit and streams the sample array into the file.  ``format="v5"`` writes
-    a scipy MATLAB v5 file instead (each variable must then stay under 2 GB)."""
+    a scipy MATLAB v5 file instead (each variable must then stay under 2 GB).
+
+    A multi-DLA run (``max_dlas`` = D > 1) also writes MULTI_DLA_VARIABLES, and its arrays have the
+    shapes ``process_qsos`` documents: h5py then sees ``sample_log_likelihoods_dla`` as (D, S, Q) --
+    ``[0]`` the first DLA, ``[1]`` the second, calc_cddf.py:89-90,107 -- and ``base_sample_inds`` as
+    (S, Q) for D = 2.  The 3-D array is written in one piece (not streamed)."""
     mat = {}
-    for key in PROCESSED_VARIABLES:
+    multi = int(np.ravel(out.get("max_dlas", 1))[0]) > 1
+    for key in PROCESSED_VARIABLES + (MULTI_DLA_VARIABLES if multi else ()):
         if key not in out:
             continue
         v = out[key]
@@ -303,7 +395,7 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
                      dla_catalog_name: str, prior_ind, release: str, test_set_name: str, test_ind,
                      params: Parameters | None = None, device: int = 0, save: bool = True,
                      rank: int = 0, world: int = 1, compute=None, timings: dict | None = None,
-                     chunk_rows: int | None = None) -> dict:
+                     chunk_rows: int | None = None, max_dlas: int = 1) -> dict:
     """The whole ``process_qsos`` script (process_qsos.m:1-249) on files laid out as the reference
     lays them out (set_parameters.m:79-86):
 
@@ -332,8 +424,14 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
     ``timings`` (a dict) receives this rank's wall seconds per phase: load (the four input files,
     process_qsos.m:1-63), compute (the engine, :88-212) and write (priors / posteriors and the
     v7.3 file, :222-249).
-    Rank 0 returns the saved scalars; other ranks their local results."""
+    Rank 0 returns the saved scalars; other ranks their local results.
+    ``max_dlas`` > 1 runs the multi-DLA search (see ``process_qsos``) on one GPU only: the sharded
+    writer is 2-D, so ``world`` > 1 raises NotImplementedError."""
     import time
+    if not 1 <= int(max_dlas) <= 4:
+        raise ValueError("max_dlas must be 1..4")
+    if max_dlas > 1 and world > 1:
+        raise NotImplementedError("max_dlas > 1 with world > 1: the sharded writer takes the 2-D sample array only")
     from .matv73 import LazyArray, LazyMat, auto_chunk_rows, is_matv73, loadmat, write_chunks
     from .shard import block_lpt_shards, expected_pixels, merge_shards
     compute = compute or _engine_compute
@@ -378,11 +476,12 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
         eng = Engine(model, samples, params, device=device)
         tm["engine_create_s"] = time.perf_counter() - t_load
         try:
-            res = eng.process(packed, want_samples=True, timings=tm)
+            res = (eng.process_multi(packed, max_dlas, want_samples=True) if max_dlas > 1 else
+                   eng.process(packed, want_samples=True, timings=tm))
         finally:
             eng.close()
     else:
-        res = compute(model, samples, packed, params, device)
+        res = compute(model, samples, packed, params, device, **(dict(max_dlas=max_dlas) if max_dlas > 1 else {}))
     t_comp = time.perf_counter()
     tm["compute_s"] = t_comp - t_load
     meta = dict(training_release=training_release, training_set_name=training_set_name,
@@ -391,7 +490,7 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
     prior = dict(z_qsos=pz, dla_ind=pdla, z_dlas=pzd)
     path = f"{rdir}/processed_qsos_{test_set_name}.mat"
     if world == 1:
-        out = _finish(res, z_all, prior, params, meta)
+        out = _finish(res, z_all, prior, params, meta, max_dlas)
         out["test_ind"] = tind
         if save:
             save_processed_qsos(path, out)

@@ -185,6 +185,64 @@ int gpdla_engine_get_stats_n(gpdla_engine* engine, gpdla_stats* stats, int64_t s
 int gpdla_engine_reset_stats(gpdla_engine* engine);
 void gpdla_engine_destroy(gpdla_engine* engine);
 
+/* ---- Multi-DLA search (Ho, Bird & Garnett 2020, arXiv:2003.11036; DESIGN.md "Multi-DLA") ---------
+ * Level 1 is gpdla_engine_process's single-DLA model.  At level d = 2..max_dlas sample j holds d
+ * DLAs: its own (z_j, N_j) and the d - 1 of a base sample b_d(j) drawn from the level-(d-1) posterior
+ * of the same spectrum by inverse-CDF resampling with the uniform resample_uniforms[(d-2) S + j].  The
+ * absorption is the product of the d separately broadened profiles; a sample closer than
+ * min_z_separation in z to one of its base DLAs is NaN; the level's evidence is the log-mean-exp over
+ * its non-NaN samples minus (d-1) occam_log_penalty.  A level below which no sample is finite is NaN
+ * with base indices -1, as is every deeper one.  Sample indices are in the caller's sample order.
+ * Fused fp64 path with num_lines = 3 only (GPDLA_EUNSUPPORTED otherwise when max_dlas > 1). */
+#define GPDLA_MAX_DLAS 4
+typedef struct gpdla_multi_dla {
+  int32_t max_dlas;                  /* D, 1..GPDLA_MAX_DLAS */
+  double min_z_separation;           /* kms_to_z(3000) in the reference lineage */
+  double occam_log_penalty;          /* per additional DLA; log(S) is the paper's Occam factor */
+  const double* resample_uniforms;   /* host [(D-1) x S] in [0, 1), one row per level; NULL if D = 1 */
+  const int32_t* forced_base_inds;   /* host [D-1][Q][S], 0-based, -1 = none; or NULL.  When given the
+                                        resampler is skipped (tests, replaying a saved run) */
+} gpdla_multi_dla;
+
+typedef struct gpdla_results_multi {
+  int32_t memory;                      /* GPDLA_MEM_HOST or GPDLA_MEM_DEVICE */
+  double* log_likelihoods_no_dla;      /* [Q] */
+  double* log_likelihoods_dla;         /* [D][Q] */
+  double* sample_log_likelihoods_dla;  /* [D][Q][sample_ld], or NULL */
+  int64_t sample_ld;                   /* >= S */
+  int32_t* base_sample_inds;           /* [D-1][Q][sample_ld] 0-based, -1 = none; or NULL */
+  double* min_z_dlas;                  /* [Q] (may be NULL) */
+  double* max_z_dlas;                  /* [Q] (may be NULL) */
+  int32_t* num_pixels;                 /* [Q] (may be NULL) */
+} gpdla_results_multi;
+
+/* Kernel times of gpdla_engine_process_multi (HIP events), cumulative since create / reset_stats.
+ * level_ms[0] is the level-1 likelihood time (the same span gpdla_stats::likelihood_ms counts);
+ * level_ms[d-1], d >= 2, spans the level-d sweep; resample_ms the resampling / chain kernels and
+ * multi_reduce_ms the NaN-aware log-mean-exp of the levels >= 2. */
+typedef struct gpdla_multi_stats {
+  double level_ms[GPDLA_MAX_DLAS];
+  int64_t level_launches[GPDLA_MAX_DLAS];
+  double resample_ms;
+  int64_t resample_launches;
+  double multi_reduce_ms;
+  int64_t multi_reduce_launches;
+} gpdla_multi_stats;
+
+/* All levels for all spectra.  Spectra go through in device batches, each drained before the next
+ * (no copy pipeline).  Host or device memory as in gpdla_engine_process; with device results the call
+ * still returns only after the last batch has finished.  Returns GPDLA_ENUMERIC like
+ * gpdla_engine_process (a non-positive pivot; the designated NaNs above do not count). */
+int gpdla_engine_process_multi(gpdla_engine* engine, const gpdla_spectra* spectra,
+                               const gpdla_multi_dla* multi, const gpdla_results_multi* results);
+int gpdla_engine_get_multi_stats(gpdla_engine* engine, gpdla_multi_stats* stats);
+/* The resampler alone, host buffers: for each of `rows` rows of S log likelihoods (row stride ld),
+ * w_i = exp(ll_i - max), NaN -> 0, C the inclusive prefix sum; out_inds[r * S + j] = the smallest i
+ * with C_i > u[j] C_{S-1} (the last i with w_i > 0 if rounding leaves none), or -1 for every j of a
+ * row whose weight sum is 0 or not finite.  u: [S] in [0, 1). */
+int gpdla_resample_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
+                       const double* u, int32_t* out_inds);
+
 /* voigt MEX replacement (voigt.c:253-304).  Host buffers.  out has n_padded - 6 values. */
 int gpdla_voigt_f64(const double* lambdas, int64_t n_padded, double z, double N,
                     int32_t num_lines, double* out);
