@@ -95,6 +95,20 @@ class MultiStats(C.Structure):
                 ("multi_reduce_ms", C.c_double), ("multi_reduce_launches", C.c_int64)]
 
 
+SUMMARY_PLANES = 5
+SUMMARY_MAX_BINS = 1024
+
+
+class SummarySpec(C.Structure):
+    _fields_ = [("log_nhi_samples", dp), ("num_z_bins", C.c_int32), ("num_nhi_bins", C.c_int32),
+                ("z_edges", dp), ("log_nhi_edges", dp)]
+
+
+class Summaries(C.Structure):
+    _fields_ = [("memory", C.c_int32), ("map_sample_inds", i32p), ("map_log_likelihoods", dp),
+                ("map_z_dlas", dp), ("map_log_nhis", dp), ("bin_planes", dp)]
+
+
 class DlaPrior(C.Structure):
     _fields_ = [("alpha", C.c_double), ("uniform_min", C.c_double), ("uniform_max", C.c_double),
                 ("fit_min", C.c_double), ("fit_max", C.c_double), ("fit_upper", C.c_double)]
@@ -122,6 +136,12 @@ SIGNATURES = {
     "gpdla_engine_process_multi": (C.c_int, [C.c_void_p, C.POINTER(Spectra), C.POINTER(MultiDla),
                                              C.POINTER(ResultsMulti)]),
     "gpdla_engine_get_multi_stats": (C.c_int, [C.c_void_p, C.POINTER(MultiStats)]),
+    "gpdla_engine_process_summaries": (C.c_int, [C.c_void_p, C.POINTER(Spectra), C.POINTER(MultiDla),
+                                                 C.POINTER(ResultsMulti), C.POINTER(SummarySpec),
+                                                 C.POINTER(Summaries)]),
+    "gpdla_engine_get_summary_stats": (C.c_int, [C.c_void_p, dp, i64p]),
+    "gpdla_posterior_summary_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, dp, i32p,
+                                              C.c_int32, C.POINTER(SummarySpec), i32p, dp, dp, dp, dp]),
     "gpdla_resample_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, i32p]),
     "gpdla_voigt_f64": (C.c_int, [dp, C.c_int64, C.c_double, C.c_double, C.c_int32, dp]),
     "gpdla_voigt_batch_f64": (C.c_int, [dp, C.c_int64, dp, dp, C.c_int64, C.c_int32, dp]),

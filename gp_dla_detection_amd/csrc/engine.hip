@@ -97,7 +97,8 @@ int grow(T** p, size_t* cap, size_t count) {
 struct TimedLaunch {
   hipEvent_t start, stop;
   int kind;  // 0 prep, 1 likelihood, 2 reduce, 3 contraction (panel-GEMM paths, inside 1);
-             // gpdla_engine_process_multi only: 4 resample, 5 level >= 2 sweep, 6 its log-mean-exp
+             // gpdla_engine_process_multi only: 4 resample, 5 level >= 2 sweep, 6 its log-mean-exp;
+             // 7 posterior summaries (gpdla_engine_process_summaries)
   int level; // multi-DLA level the span also counts for in gpdla_multi_stats (0: none)
 };
 
@@ -197,6 +198,15 @@ struct gpdla_engine {
          cap_m_chain[2] = {0, 0}, cap_m_forced = 0;
   gpdla_multi_stats mstats{};
 
+  // posterior summaries (gpdla_engine_process_summaries): the samples' log10 N_HI and the grid edges of
+  // a call, and a batch's outputs ([D][nq] MAP index / value, [D][nq][kMaxDlas] pairs, [nq][5][bins])
+  double *d_s_lognhi = nullptr, *d_s_edges = nullptr, *d_s_ll = nullptr, *d_s_z = nullptr, *d_s_n = nullptr,
+         *d_s_planes = nullptr;
+  int32_t* d_s_ind = nullptr;
+  size_t cap_s_lognhi = 0, cap_s_edges = 0, cap_s_ll = 0, cap_s_z = 0, cap_s_n = 0, cap_s_planes = 0, cap_s_ind = 0;
+  double summary_ms = 0.0;
+  int64_t summary_launches = 0;
+
   std::vector<TimedLaunch> pending;
   gpdla_stats stats{};
 };
@@ -222,6 +232,7 @@ int resolve_events(gpdla_engine* e) {
     if (t.kind == 3) { e->stats.contraction_ms += ms; e->stats.contraction_launches++; }
     if (t.kind == 4) { e->mstats.resample_ms += ms; e->mstats.resample_launches++; }
     if (t.kind == 6) { e->mstats.multi_reduce_ms += ms; e->mstats.multi_reduce_launches++; }
+    if (t.kind == 7) { e->summary_ms += ms; e->summary_launches++; }
     if (t.level >= 1 && t.level <= GPDLA_MAX_DLAS) {
       e->mstats.level_ms[t.level - 1] += ms;
       e->mstats.level_launches[t.level - 1]++;
@@ -324,7 +335,8 @@ void gpdla_engine_destroy(gpdla_engine* e) {
                   e->d_wg, e->d_wu, e->d_G, e->d_U, e->d_q1p, e->d_ldp, e->d_pi8, e->d_psc,
                   e->d_pent, e->d_ai8, e->d_off_c, e->d_nhi_c, e->d_m_sll, e->d_m_lldla, e->d_m_null,
                   e->d_m_zmin, e->d_m_zmax, e->d_m_u, e->d_m_cws, e->d_m_npix, e->d_m_base,
-                  e->d_m_chain[0], e->d_m_chain[1], e->d_m_forced};
+                  e->d_m_chain[0], e->d_m_chain[1], e->d_m_forced, e->d_s_lognhi, e->d_s_edges,
+                  e->d_s_ll, e->d_s_z, e->d_s_n, e->d_s_planes, e->d_s_ind};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (e->h_meta) (void)hipHostFree(e->h_meta);
@@ -1003,6 +1015,8 @@ int gpdla_engine_reset_stats(gpdla_engine* e) {
   if (rc) return rc;
   e->stats = gpdla_stats{};
   e->mstats = gpdla_multi_stats{};
+  e->summary_ms = 0.0;
+  e->summary_launches = 0;
   return GPDLA_OK;
 }
 
@@ -1043,9 +1057,45 @@ static int multi_caller_samples(gpdla_engine* e) {
   return GPDLA_OK;
 }
 
-int gpdla_engine_process_multi(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
-                               const gpdla_results_multi* res) {
+// the grid of a summary call: GPDLA_EINVAL unless it is absent (0 x 0) or well formed
+static int validate_summary_grid(const gpdla_summary_spec* spec) {
+  const int64_t nz = spec->num_z_bins, nn = spec->num_nhi_bins;
+  if (nz < 0 || nn < 0 || (nz == 0) != (nn == 0))
+    return set_error(GPDLA_EINVAL, "summary grid %lld x %lld: both bin counts must be positive, or both 0", (long long)nz,
+                     (long long)nn);
+  if (nz * nn > GPDLA_SUMMARY_MAX_BINS)
+    return set_error(GPDLA_EINVAL, "summary grid %lld x %lld exceeds %d bins", (long long)nz, (long long)nn,
+                     GPDLA_SUMMARY_MAX_BINS);
+  if (nz == 0) return GPDLA_OK;
+  if (!spec->z_edges || !spec->log_nhi_edges) return set_error(GPDLA_EINVAL, "null summary edge array");
+  for (int ax = 0; ax < 2; ++ax) {
+    const double* ed = ax ? spec->log_nhi_edges : spec->z_edges;
+    const int64_t n = ax ? nn : nz;
+    for (int64_t i = 0; i <= n; ++i)
+      if (!std::isfinite(ed[i]) || (i > 0 && !(ed[i] > ed[i - 1])))
+        return set_error(GPDLA_EINVAL, "%s[%lld] = %g: edges must be finite and strictly increasing",
+                         ax ? "log_nhi_edges" : "z_edges", (long long)i, ed[i]);
+  }
+  return GPDLA_OK;
+}
+
+// gpdla_engine_process_multi, and with spec / sums gpdla_engine_process_summaries: the summary kernel
+// runs per batch after the last level, on the level workspaces the batch leaves on the device
+static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
+                              const gpdla_results_multi* res, const gpdla_summary_spec* spec,
+                              const gpdla_summaries* sums) {
   if (!e || !sp || !mu || !res) return set_error(GPDLA_EINVAL, "null argument");
+  if (spec) {
+    if (!sums) return set_error(GPDLA_EINVAL, "null argument");
+    int rcv = validate_summary_grid(spec);
+    if (rcv) return rcv;
+    if (!spec->log_nhi_samples) return set_error(GPDLA_EINVAL, "null log_nhi_samples");
+    if (!sums->map_sample_inds || !sums->map_log_likelihoods || !sums->map_z_dlas || !sums->map_log_nhis)
+      return set_error(GPDLA_EINVAL, "null summary array");
+    if (spec->num_z_bins > 0 && !sums->bin_planes) return set_error(GPDLA_EINVAL, "null bin_planes with a grid");
+    if (sums->memory != GPDLA_MEM_HOST && sums->memory != GPDLA_MEM_DEVICE)
+      return set_error(GPDLA_EINVAL, "summaries memory=%d", sums->memory);
+  }
   const int D = mu->max_dlas;
   if (D < 1 || D > GPDLA_MAX_DLAS) return set_error(GPDLA_EINVAL, "max_dlas=%d outside 1..%d", D, GPDLA_MAX_DLAS);
   if (D > 1 && (e->gemm || e->i8))
@@ -1074,8 +1124,19 @@ int gpdla_engine_process_multi(gpdla_engine* e, const gpdla_spectra* sp, const g
     return set_error(GPDLA_EINVAL, "sample_ld (%lld) < num_samples (%lld)", (long long)res->sample_ld, (long long)S);
   HIP_TRY(hipSetDevice(e->device));
   int rc;
-  if (D > 1 && (rc = multi_caller_samples(e))) return rc;
+  if ((D > 1 || spec) && (rc = multi_caller_samples(e))) return rc;
   hipStream_t st = e->stream;
+  const int nzb = spec ? spec->num_z_bins : 0, nnb = spec ? spec->num_nhi_bins : 0;
+  const size_t nbins = (size_t)nzb * nnb;
+  if (spec) {
+    if ((rc = grow(&e->d_s_lognhi, &e->cap_s_lognhi, (size_t)S))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_s_lognhi, spec->log_nhi_samples, (size_t)S * 8, hipMemcpyHostToDevice, st));
+    if (nbins) {
+      if ((rc = grow(&e->d_s_edges, &e->cap_s_edges, (size_t)(nzb + nnb + 2)))) return rc;
+      HIP_TRY(hipMemcpyAsync(e->d_s_edges, spec->z_edges, (size_t)(nzb + 1) * 8, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(e->d_s_edges + nzb + 1, spec->log_nhi_edges, (size_t)(nnb + 1) * 8, hipMemcpyHostToDevice, st));
+    }
+  }
   const bool out_dev = res->memory == GPDLA_MEM_DEVICE;
   const hipMemcpyKind out_kind = out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   const bool forced = D > 1 && mu->forced_base_inds;
@@ -1165,6 +1226,38 @@ int gpdla_engine_process_multi(gpdla_engine* e, const gpdla_spectra* sp, const g
       e->pending.push_back(t6);
     }
 
+    if (spec) {
+      if ((rc = grow(&e->d_s_ind, &e->cap_s_ind, (size_t)nq * D))) return rc;
+      if ((rc = grow(&e->d_s_ll, &e->cap_s_ll, (size_t)nq * D))) return rc;
+      if ((rc = grow(&e->d_s_z, &e->cap_s_z, (size_t)nq * D * kMaxDlas))) return rc;
+      if ((rc = grow(&e->d_s_n, &e->cap_s_n, (size_t)nq * D * kMaxDlas))) return rc;
+      if (nbins && (rc = grow(&e->d_s_planes, &e->cap_s_planes, (size_t)nq * kSummaryPlanes * nbins))) return rc;
+      SummaryArgs sa{};
+      sa.rows = (int32_t)nq; sa.levels = D; sa.ll = e->d_m_sll; sa.ld = S; sa.S = S;
+      sa.base = D > 1 ? e->d_m_base : nullptr; sa.ld_base = S;
+      sa.offset = e->d_off_c; sa.log_nhi = e->d_s_lognhi; sa.nhi = e->d_nhi_c;
+      sa.zmin = e->d_m_zmin; sa.zmax = e->d_m_zmax;
+      sa.nz = nzb; sa.nn = nnb; sa.z_edges = e->d_s_edges; sa.n_edges = nbins ? e->d_s_edges + nzb + 1 : nullptr;
+      sa.map_ind = e->d_s_ind; sa.map_ll = e->d_s_ll; sa.map_z = e->d_s_z; sa.map_n = e->d_s_n;
+      sa.planes = nbins ? e->d_s_planes : nullptr;
+      TimedLaunch t7{};
+      if ((rc = record_start(e, &t7, 7))) return rc;
+      HIP_TRY(launch_posterior_summary(sa, st));
+      HIP_TRY(hipEventRecord(t7.stop, st));
+      e->pending.push_back(t7);
+      const hipMemcpyKind sk = sums->memory == GPDLA_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+      for (int d = 0; d < D; ++d) {
+        const int64_t o = (int64_t)d * Q + q0;
+        HIP_TRY(hipMemcpyAsync(sums->map_sample_inds + o, e->d_s_ind + (size_t)d * nq, nq * 4, sk, st));
+        HIP_TRY(hipMemcpyAsync(sums->map_log_likelihoods + o, e->d_s_ll + (size_t)d * nq, nq * 8, sk, st));
+        HIP_TRY(hipMemcpyAsync(sums->map_z_dlas + o * kMaxDlas, e->d_s_z + (size_t)d * nq * kMaxDlas, nq * kMaxDlas * 8, sk, st));
+        HIP_TRY(hipMemcpyAsync(sums->map_log_nhis + o * kMaxDlas, e->d_s_n + (size_t)d * nq * kMaxDlas, nq * kMaxDlas * 8, sk, st));
+      }
+      if (nbins)
+        HIP_TRY(hipMemcpyAsync(sums->bin_planes + (size_t)q0 * kSummaryPlanes * nbins, e->d_s_planes,
+                               (size_t)nq * kSummaryPlanes * nbins * 8, sk, st));
+    }
+
     HIP_TRY(hipMemcpyAsync(res->log_likelihoods_no_dla + q0, e->d_m_null, nq * 8, out_kind, st));
     if (res->min_z_dlas) HIP_TRY(hipMemcpyAsync(res->min_z_dlas + q0, e->d_m_zmin, nq * 8, out_kind, st));
     if (res->max_z_dlas) HIP_TRY(hipMemcpyAsync(res->max_z_dlas + q0, e->d_m_zmax, nq * 8, out_kind, st));
@@ -1183,6 +1276,103 @@ int gpdla_engine_process_multi(gpdla_engine* e, const gpdla_spectra* sp, const g
     HIP_TRY(hipStreamSynchronize(st));
   }
   return gpdla_engine_synchronize(e);
+}
+
+int gpdla_engine_process_multi(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
+                               const gpdla_results_multi* res) {
+  return process_multi_impl(e, sp, mu, res, nullptr, nullptr);
+}
+
+int gpdla_engine_process_summaries(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
+                                   const gpdla_results_multi* res, const gpdla_summary_spec* spec,
+                                   const gpdla_summaries* sums) {
+  if (!spec || !sums) return set_error(GPDLA_EINVAL, "null argument");
+  return process_multi_impl(e, sp, mu, res, spec, sums);
+}
+
+int gpdla_engine_get_summary_stats(gpdla_engine* e, double* ms, int64_t* launches) {
+  if (!e || !ms || !launches) return set_error(GPDLA_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  int rc = resolve_events(e);
+  if (rc) return rc;
+  *ms = e->summary_ms;
+  *launches = e->summary_launches;
+  return GPDLA_OK;
+}
+
+int gpdla_posterior_summary_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
+                                const double* offset_samples, const double* log_nhi_samples,
+                                const double* nhi_samples, const double* min_z, const double* max_z,
+                                const int32_t* base_inds, int32_t levels, const gpdla_summary_spec* spec,
+                                int32_t* map_sample_inds, double* map_log_likelihoods, double* map_z_dlas,
+                                double* map_log_nhis, double* bin_planes) {
+  if (!ll || !offset_samples || !log_nhi_samples || !nhi_samples || !min_z || !max_z || !spec || !map_sample_inds ||
+      !map_log_likelihoods || !map_z_dlas || !map_log_nhis)
+    return set_error(GPDLA_EINVAL, "null argument");
+  if (rows < 0 || S < 1 || ld < S || rows > INT32_MAX || S > INT32_MAX)
+    return set_error(GPDLA_EINVAL, "rows=%lld S=%lld ld=%lld", (long long)rows, (long long)S, (long long)ld);
+  if (levels < 1 || levels > GPDLA_MAX_DLAS) return set_error(GPDLA_EINVAL, "levels=%d outside 1..%d", levels, GPDLA_MAX_DLAS);
+  if (levels > 1 && !base_inds) return set_error(GPDLA_EINVAL, "levels=%d needs base_inds", levels);
+  int rc = validate_summary_grid(spec);
+  if (rc) return rc;
+  const int nz = spec->num_z_bins, nn = spec->num_nhi_bins;
+  const size_t nbins = (size_t)nz * nn;
+  if (nbins && !bin_planes) return set_error(GPDLA_EINVAL, "null bin_planes with a grid");
+  if ((rc = check_device(device))) return rc;
+  if (rows == 0) return GPDLA_OK;
+  HIP_TRY(hipSetDevice(device));
+  const size_t R = (size_t)rows, LV = (size_t)levels;
+  // one device allocation, carved in 256-byte steps
+  size_t off = 0;
+  auto carve = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+  const size_t o_ll = carve(LV * R * ld * 8), o_base = carve(levels > 1 ? (LV - 1) * R * ld * 4 : 0);
+  const size_t o_off = carve((size_t)S * 8), o_ln = carve((size_t)S * 8), o_nh = carve((size_t)S * 8);
+  const size_t o_zmin = carve(R * 8), o_zmax = carve(R * 8), o_ed = carve((size_t)(nz + nn + 2) * 8);
+  const size_t o_ind = carve(LV * R * 4), o_mll = carve(LV * R * 8);
+  const size_t o_mz = carve(LV * R * kMaxDlas * 8), o_mn = carve(LV * R * kMaxDlas * 8);
+  const size_t o_pl = carve(R * kSummaryPlanes * nbins * 8);
+  char* d = nullptr;
+  auto done = [&](int code) {
+    if (d) (void)hipFree(d);
+    return code;
+  };
+#define TRY_S(expr)                                                                                          \
+  do {                                                                                                       \
+    hipError_t e_ = (expr);                                                                                  \
+    if (e_ != hipSuccess)                                                                                    \
+      return done(set_error(e_ == hipErrorOutOfMemory ? GPDLA_ENOMEM : GPDLA_EDEVICE, "posterior_summary: %s failed: %s", \
+                            #expr, hipGetErrorString(e_)));                                                  \
+  } while (0)
+  TRY_S(hipMalloc((void**)&d, off));
+  TRY_S(hipMemcpy(d + o_ll, ll, LV * R * ld * 8, hipMemcpyHostToDevice));
+  if (levels > 1) TRY_S(hipMemcpy(d + o_base, base_inds, (LV - 1) * R * ld * 4, hipMemcpyHostToDevice));
+  TRY_S(hipMemcpy(d + o_off, offset_samples, (size_t)S * 8, hipMemcpyHostToDevice));
+  TRY_S(hipMemcpy(d + o_ln, log_nhi_samples, (size_t)S * 8, hipMemcpyHostToDevice));
+  TRY_S(hipMemcpy(d + o_nh, nhi_samples, (size_t)S * 8, hipMemcpyHostToDevice));
+  TRY_S(hipMemcpy(d + o_zmin, min_z, R * 8, hipMemcpyHostToDevice));
+  TRY_S(hipMemcpy(d + o_zmax, max_z, R * 8, hipMemcpyHostToDevice));
+  if (nbins) {
+    TRY_S(hipMemcpy(d + o_ed, spec->z_edges, (size_t)(nz + 1) * 8, hipMemcpyHostToDevice));
+    TRY_S(hipMemcpy(d + o_ed + (size_t)(nz + 1) * 8, spec->log_nhi_edges, (size_t)(nn + 1) * 8, hipMemcpyHostToDevice));
+  }
+  SummaryArgs sa{};
+  sa.rows = (int32_t)rows; sa.levels = levels; sa.ll = (const double*)(d + o_ll); sa.ld = ld; sa.S = S;
+  sa.base = levels > 1 ? (const int32_t*)(d + o_base) : nullptr; sa.ld_base = ld;
+  sa.offset = (const double*)(d + o_off); sa.log_nhi = (const double*)(d + o_ln); sa.nhi = (const double*)(d + o_nh);
+  sa.zmin = (const double*)(d + o_zmin); sa.zmax = (const double*)(d + o_zmax);
+  sa.nz = nz; sa.nn = nn; sa.z_edges = (const double*)(d + o_ed); sa.n_edges = (const double*)(d + o_ed) + nz + 1;
+  sa.map_ind = (int32_t*)(d + o_ind); sa.map_ll = (double*)(d + o_mll);
+  sa.map_z = (double*)(d + o_mz); sa.map_n = (double*)(d + o_mn);
+  sa.planes = nbins ? (double*)(d + o_pl) : nullptr;
+  TRY_S(launch_posterior_summary(sa, nullptr));
+  TRY_S(hipMemcpy(map_sample_inds, d + o_ind, LV * R * 4, hipMemcpyDeviceToHost));
+  TRY_S(hipMemcpy(map_log_likelihoods, d + o_mll, LV * R * 8, hipMemcpyDeviceToHost));
+  TRY_S(hipMemcpy(map_z_dlas, d + o_mz, LV * R * kMaxDlas * 8, hipMemcpyDeviceToHost));
+  TRY_S(hipMemcpy(map_log_nhis, d + o_mn, LV * R * kMaxDlas * 8, hipMemcpyDeviceToHost));
+  if (nbins) TRY_S(hipMemcpy(bin_planes, d + o_pl, R * kSummaryPlanes * nbins * 8, hipMemcpyDeviceToHost));
+#undef TRY_S
+  return done(GPDLA_OK);
 }
 
 int gpdla_resample_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld, const double* u,

@@ -509,6 +509,32 @@ hipError_t launch_multi_level(int K, const MultiLevelArgs& a, hipStream_t s);
 hipError_t launch_resample(const ResampleArgs& a, hipStream_t s);
 hipError_t launch_multi_reduce(const MultiReduceArgs& a, hipStream_t s);
 
+// ---- posterior summaries (posterior_summary.hip): MAP sample and chain parameters per (row, level),
+// binned normalised masses of level 1
+constexpr int kSummaryPlanes = 5;        // sum pi, pi^2, N pi, N^2 pi, N^2 pi^2 per bin
+constexpr int kSummaryMaxBins = 1024;
+struct SummaryArgs {
+  int32_t rows, levels;
+  const double* ll;              // [levels][rows][ld], caller's sample order
+  int64_t ld, S;
+  const int32_t* base;           // [levels - 1][rows][ld_base] base indices, or nullptr (levels = 1)
+  int64_t ld_base;
+  const double* offset;          // [S] caller order
+  const double* log_nhi;         // [S]
+  const double* nhi;             // [S]
+  const double* zmin;            // [rows]
+  const double* zmax;            // [rows]
+  int32_t nz, nn;                // grid (ignored without planes)
+  const double* z_edges;         // device [nz + 1]
+  const double* n_edges;         // device [nn + 1]
+  int32_t* map_ind;              // [levels][rows]
+  double* map_ll;                // [levels][rows]
+  double* map_z;                 // [levels][rows][kMaxDlas]
+  double* map_n;                 // [levels][rows][kMaxDlas]
+  double* planes;                // [rows][kSummaryPlanes][nz nn], or nullptr: MAP only
+};
+hipError_t launch_posterior_summary(const SummaryArgs& a, hipStream_t s);
+
 // host-side table fitting (faddeeva_host.cpp)
 void fit_core_table(int line, double* core);
 void fit_wing_line(int line, double* wing);

@@ -149,6 +149,49 @@ class Engine:
         Returns ``log_likelihoods_dla`` (D x Q), ``sample_log_likelihoods_dla`` (D x Q x S),
         ``base_sample_inds`` ((D - 1) x Q x S int32, -1 = none) and the per-spectrum vectors of
         ``process``.  ``memory="device"`` routes inputs and results through device buffers (same values)."""
+        return self._run_multi(packed, max_dlas, resample_uniforms, base_sample_inds, want_samples,
+                               min_z_separation, occam_log_penalty, raise_numeric, memory, None)
+
+    def process_summaries(self, packed: dict, max_dlas: int, log_nhi_samples, z_edges=None, log_nhi_edges=None,
+                          want_samples: bool = False, **kwargs) -> dict:
+        """``process_multi`` (its keyword arguments pass through; ``max_dlas`` 1..4) with the posterior
+        summaries reduced on the device (gpdla_engine_process_summaries), so the D x Q x S sample array need
+        not leave it (``want_samples=False``, the default here).  ``log_nhi_samples`` are the engine's
+        samples' log10 N_HI.  Besides ``process_multi``'s arrays:
+
+        ``map_sample_inds`` (D x Q int32)  first maximum over the non-NaN samples of each level, -1 = none
+        ``map_log_likelihoods`` (D x Q)    that maximum (NaN)
+        ``MAP_z_dlas`` / ``MAP_log_nhis`` (D x Q x D)  level d's d (z_DLA, log N_HI) pairs: the MAP sample's
+                                           own, then its base chain's; unused slots NaN
+        ``bin_planes`` (Q x 5 x nz x nn)   with ``z_edges`` (nz + 1) and ``log_nhi_edges`` (nn + 1): the
+                                           level-1 normalised sample masses summed per bin as sum pi, pi^2,
+                                           N pi, N^2 pi, N^2 pi^2 (``catalog.cddf_moments`` consumes them)
+        Repeated calls and any ``max_batch_spectra`` give bitwise equal summaries."""
+        if (z_edges is None) != (log_nhi_edges is None):
+            raise ValueError("z_edges and log_nhi_edges go together")
+        lognhi = np.ascontiguousarray(log_nhi_samples, dtype=np.float64).ravel()
+        if lognhi.size != self.num_samples:
+            raise ValueError("one log_nhi sample per engine sample")
+        summary = dict(log_nhi=lognhi,
+                       z_edges=None if z_edges is None else np.ascontiguousarray(z_edges, dtype=np.float64).ravel(),
+                       n_edges=None if log_nhi_edges is None else np.ascontiguousarray(log_nhi_edges, dtype=np.float64).ravel())
+        order = ("resample_uniforms", "base_sample_inds", "min_z_separation", "occam_log_penalty", "raise_numeric", "memory")
+        unknown = set(kwargs) - set(order)
+        if unknown:
+            raise TypeError(f"unexpected keyword arguments {sorted(unknown)}")
+        return self._run_multi(packed, max_dlas, kwargs.get("resample_uniforms"), kwargs.get("base_sample_inds"),
+                               want_samples, kwargs.get("min_z_separation"), kwargs.get("occam_log_penalty"),
+                               kwargs.get("raise_numeric", False), kwargs.get("memory", "host"), summary)
+
+    def summary_stats(self) -> dict:
+        """gpdla_engine_get_summary_stats: cumulative ms and count of the summary launches."""
+        ms, n = C.c_double(0.0), C.c_int64(0)
+        L.check(self.lib.gpdla_engine_get_summary_stats(self._h, C.byref(ms), C.byref(n)))
+        return dict(summary_ms=ms.value, summary_launches=n.value)
+
+    def _run_multi(self, packed, max_dlas, resample_uniforms, base_sample_inds, want_samples, min_z_separation,
+                   occam_log_penalty, raise_numeric, memory, summary) -> dict:
+        """process_multi / process_summaries: ``summary`` is None or the samples' log N_HI and the grid."""
         D, S = int(max_dlas), self.num_samples
         offsets = np.ascontiguousarray(packed["offsets"], dtype=np.int64)
         Q = offsets.size - 1
@@ -184,6 +227,23 @@ class Engine:
         if want_samples:
             out["sample_log_likelihoods_dla"] = np.full((Dc, Q, S), np.nan)
             out["base_sample_inds"] = np.full((Dc - 1, Q, S), -1, dtype=np.int32)
+        spec = None
+        if summary is not None:
+            ez, en = summary["z_edges"], summary["n_edges"]
+            nz, nn = (0, 0) if ez is None else (ez.size - 1, en.size - 1)
+            spec = L.SummarySpec(log_nhi_samples=L.ptr(summary["log_nhi"]), num_z_bins=nz, num_nhi_bins=nn,
+                                 z_edges=L.ptr(ez), log_nhi_edges=L.ptr(en))
+            sout = dict(map_sample_inds=np.full((Dc, Q), -1, dtype=np.int32), map_log_likelihoods=np.full((Dc, Q), np.nan),
+                        map_z_dlas=np.full((Dc, Q, L.MAX_DLAS), np.nan), map_log_nhis=np.full((Dc, Q, L.MAX_DLAS), np.nan))
+            if ez is not None:
+                sout["bin_planes"] = np.zeros((Q, L.SUMMARY_PLANES, max(nz, 0), max(nn, 0)))
+
+        def call(sp, rs, sm):
+            if spec is None:
+                return self.lib.gpdla_engine_process_multi(self._h, C.byref(sp), C.byref(md), C.byref(rs))
+            return self.lib.gpdla_engine_process_summaries(self._h, C.byref(sp), C.byref(md), C.byref(rs),
+                                                           C.byref(spec), C.byref(sm))
+        sm = None
         if memory == "host":
             sp = L.Spectra(memory=L.MEM_HOST, num_spectra=Q, offsets=L.ptr(offsets, C.c_int64),
                            wavelengths=L.ptr(wl), flux=L.ptr(fl), noise_variance=L.ptr(nv),
@@ -195,7 +255,13 @@ class Engine:
                                 base_sample_inds=L.ptr(base, C.c_int32) if base is not None and base.size else None,
                                 min_z_dlas=L.ptr(out["min_z_dlas"]), max_z_dlas=L.ptr(out["max_z_dlas"]),
                                 num_pixels=L.ptr(out["num_pixels"], C.c_int32))
-            rc = self.lib.gpdla_engine_process_multi(self._h, C.byref(sp), C.byref(md), C.byref(rs))
+            if spec is not None:
+                pl = sout.get("bin_planes")
+                sm = L.Summaries(memory=L.MEM_HOST, map_sample_inds=L.ptr(sout["map_sample_inds"], C.c_int32),
+                                 map_log_likelihoods=L.ptr(sout["map_log_likelihoods"]),
+                                 map_z_dlas=L.ptr(sout["map_z_dlas"]), map_log_nhis=L.ptr(sout["map_log_nhis"]),
+                                 bin_planes=L.ptr(pl) if pl is not None and pl.size else None)
+            rc = call(sp, rs, sm)
         elif memory == "device":
             dev = {k: L.DeviceArray.from_numpy(v, self.device) for k, v in
                    dict(wl=wl, fl=fl, nv=nv, mk=mk, zq=zq).items()}
@@ -214,11 +280,22 @@ class Engine:
                                 base_sample_inds=dptr("base_sample_inds", C.c_int32),
                                 min_z_dlas=dptr("min_z_dlas"), max_z_dlas=dptr("max_z_dlas"),
                                 num_pixels=dptr("num_pixels", C.c_int32))
-            rc = self.lib.gpdla_engine_process_multi(self._h, C.byref(sp), C.byref(md), C.byref(rs))
+            dsum = {}
+            if spec is not None:
+                dsum = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in sout.items() if v.size}
+
+                def sptr(key, ctype=C.c_double):
+                    return L.dev_ptr(dsum[key].ptr, ctype) if key in dsum else None
+                sm = L.Summaries(memory=L.MEM_DEVICE, map_sample_inds=sptr("map_sample_inds", C.c_int32),
+                                 map_log_likelihoods=sptr("map_log_likelihoods"), map_z_dlas=sptr("map_z_dlas"),
+                                 map_log_nhis=sptr("map_log_nhis"), bin_planes=sptr("bin_planes"))
+            rc = call(sp, rs, sm)
             if rc in (L.GPDLA_OK, L.GPDLA_ENUMERIC):
                 for k, d in dout.items():
                     out[k] = d.numpy()
-            for d in list(dev.values()) + list(dout.values()):
+                for k, d in dsum.items():
+                    sout[k] = d.numpy()
+            for d in list(dev.values()) + list(dout.values()) + list(dsum.values()):
                 d.free()
         else:
             raise ValueError("memory must be 'host' or 'device'")
@@ -226,6 +303,12 @@ class Engine:
             out["numeric_warning"] = self.lib.gpdla_last_error().decode()
         else:
             L.check(rc)
+        if spec is not None:
+            out["map_sample_inds"], out["map_log_likelihoods"] = sout["map_sample_inds"], sout["map_log_likelihoods"]
+            out["MAP_z_dlas"] = np.ascontiguousarray(sout["map_z_dlas"][:, :, :Dc])
+            out["MAP_log_nhis"] = np.ascontiguousarray(sout["map_log_nhis"][:, :, :Dc])
+            if "bin_planes" in sout:
+                out["bin_planes"] = sout["bin_planes"]
         return out
 
     def multi_stats(self) -> dict:
@@ -321,6 +404,56 @@ def resample(log_likelihoods, uniforms, device: int = 0) -> np.ndarray:
         raise ValueError("one uniform per sample")
     out = np.empty((rows, S), dtype=np.int32)
     L.check(L.load().gpdla_resample_f64(device, L.ptr(ll), rows, S, S, L.ptr(u), L.ptr(out, C.c_int32)))
+    return out
+
+
+def posterior_summary(log_likelihoods, offset_samples, log_nhi_samples, nhi_samples, min_z, max_z,
+                      base_sample_inds=None, z_edges=None, log_nhi_edges=None, device: int = 0) -> dict:
+    """The summary kernel alone (gpdla_posterior_summary_f64) on host arrays: ``log_likelihoods`` is
+    rows x S (one level) or levels x rows x S, ``base_sample_inds`` (levels - 1) x rows x S (0-based,
+    -1 = none), ``min_z`` / ``max_z`` one per row.  Returns ``Engine.process_summaries``'s summary arrays
+    (``map_sample_inds``, ``map_log_likelihoods``, ``MAP_z_dlas``, ``MAP_log_nhis`` and, with a grid,
+    ``bin_planes``)."""
+    ll = np.ascontiguousarray(log_likelihoods, dtype=np.float64)
+    if ll.ndim == 2:
+        ll = ll[None]
+    if ll.ndim != 3:
+        raise ValueError("log_likelihoods must be rows x S or levels x rows x S")
+    levels, rows, S = ll.shape
+    off = np.ascontiguousarray(offset_samples, dtype=np.float64).ravel()
+    lognhi = np.ascontiguousarray(log_nhi_samples, dtype=np.float64).ravel()
+    nhi = np.ascontiguousarray(nhi_samples, dtype=np.float64).ravel()
+    zmin = np.ascontiguousarray(np.broadcast_to(np.asarray(min_z, dtype=np.float64), (rows,)))
+    zmax = np.ascontiguousarray(np.broadcast_to(np.asarray(max_z, dtype=np.float64), (rows,)))
+    if not off.size == lognhi.size == nhi.size == S:
+        raise ValueError("sample arrays must have S entries")
+    base = None
+    if base_sample_inds is not None:
+        base = np.ascontiguousarray(base_sample_inds, dtype=np.int32)
+        if base.shape != (max(levels - 1, 0), rows, S):
+            raise ValueError(f"base_sample_inds must be {(levels - 1, rows, S)}")
+    if (z_edges is None) != (log_nhi_edges is None):
+        raise ValueError("z_edges and log_nhi_edges go together")
+    ez = None if z_edges is None else np.ascontiguousarray(z_edges, dtype=np.float64).ravel()
+    en = None if log_nhi_edges is None else np.ascontiguousarray(log_nhi_edges, dtype=np.float64).ravel()
+    nz, nn = (0, 0) if ez is None else (ez.size - 1, en.size - 1)
+    spec = L.SummarySpec(log_nhi_samples=L.ptr(lognhi), num_z_bins=nz, num_nhi_bins=nn, z_edges=L.ptr(ez),
+                         log_nhi_edges=L.ptr(en))
+    Lc = min(max(levels, 1), L.MAX_DLAS)
+    ind = np.full((levels, rows), -1, dtype=np.int32)
+    mll = np.full((levels, rows), np.nan)
+    mz = np.full((levels, rows, L.MAX_DLAS), np.nan)
+    mn = np.full((levels, rows, L.MAX_DLAS), np.nan)
+    planes = None if ez is None else np.zeros((rows, L.SUMMARY_PLANES, max(nz, 0), max(nn, 0)))
+    L.check(L.load().gpdla_posterior_summary_f64(
+        device, L.ptr(ll), rows, S, S, L.ptr(off), L.ptr(lognhi), L.ptr(nhi), L.ptr(zmin), L.ptr(zmax),
+        L.ptr(base, C.c_int32) if base is not None and base.size else None, levels, C.byref(spec),
+        L.ptr(ind, C.c_int32), L.ptr(mll), L.ptr(mz), L.ptr(mn),
+        L.ptr(planes) if planes is not None and planes.size else None))
+    out = dict(map_sample_inds=ind, map_log_likelihoods=mll, MAP_z_dlas=np.ascontiguousarray(mz[:, :, :Lc]),
+               MAP_log_nhis=np.ascontiguousarray(mn[:, :, :Lc]))
+    if planes is not None:
+        out["bin_planes"] = planes
     return out
 
 

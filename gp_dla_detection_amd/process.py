@@ -113,15 +113,60 @@ def _select(spectra, test_ind):
     return pack_spectra(lst)
 
 
+def _summary_grid(summaries):
+    """``summaries`` of process_qsos -> None (off) or (z_edges, log_nhi_edges), both None for MAP only."""
+    if summaries is None or summaries is False:
+        return None
+    if summaries is True:
+        return None, None
+    if not isinstance(summaries, dict) or set(summaries) - {"z_edges", "log_nhi_edges"}:
+        raise ValueError("summaries must be None, True or dict(z_edges=..., log_nhi_edges=...)")
+    ez, en = summaries.get("z_edges"), summaries.get("log_nhi_edges")
+    if (ez is None) != (en is None):
+        raise ValueError("summaries needs both z_edges and log_nhi_edges, or neither")
+    if ez is None:
+        return None, None
+    return np.ascontiguousarray(ez, dtype=np.float64).ravel(), np.ascontiguousarray(en, dtype=np.float64).ravel()
+
+
+def _compute_kwargs(max_dlas: int, summaries, save_samples: bool) -> dict:
+    """What a ``compute`` replacement is told beyond the five positional arguments: only what differs
+    from the plain single-DLA call, so existing replacements keep working."""
+    kw = {}
+    if max_dlas > 1:
+        kw["max_dlas"] = max_dlas
+    if _summary_grid(summaries) is not None:
+        kw["summaries"] = summaries
+    if not save_samples:
+        kw["save_samples"] = False
+    return kw
+
+
 def _engine_compute(model: dict, samples: dict, packed: dict, params: Parameters, device: int = 0,
-                    engine: Engine | None = None, max_dlas: int = 1) -> dict:
+                    engine: Engine | None = None, max_dlas: int = 1, summaries=None, save_samples: bool = True,
+                    timings: dict | None = None) -> dict:
     """The hot path on the GPU: per-spectrum null / sample / DLA log likelihoods and z ranges; with
-    ``max_dlas`` > 1 every level of the multi-DLA search (Engine.process_multi's arrays)."""
+    ``max_dlas`` > 1 every level of the multi-DLA search (Engine.process_multi's arrays); with
+    ``summaries`` the posterior summaries as well (Engine.process_summaries), the sample arrays only if
+    ``save_samples``."""
+    grid = _summary_grid(summaries)
     eng = engine or Engine(model, samples, params, device=device)
     try:
+        if grid is not None:
+            if "log_nhi_samples" not in samples:
+                raise ValueError("summaries need samples['log_nhi_samples']")
+            res = eng.process_summaries(packed, max_dlas, samples["log_nhi_samples"], z_edges=grid[0],
+                                        log_nhi_edges=grid[1], want_samples=save_samples)
+            if max_dlas == 1:   # Engine.process's shapes: no level axis, no multi-DLA variables
+                res["log_likelihoods_dla"] = res["log_likelihoods_dla"][0]
+                if "sample_log_likelihoods_dla" in res:
+                    res["sample_log_likelihoods_dla"] = res["sample_log_likelihoods_dla"][0]
+                res.pop("base_sample_inds", None)
+                res.pop("max_dlas", None)
+            return res
         if max_dlas > 1:
-            return eng.process_multi(packed, max_dlas, want_samples=True)
-        return eng.process(packed, want_samples=True)
+            return eng.process_multi(packed, max_dlas, want_samples=save_samples)
+        return eng.process(packed, want_samples=save_samples, **(dict(timings=timings) if timings is not None else {}))
     finally:
         if engine is None:
             eng.close()
@@ -165,9 +210,37 @@ def _finish_multi(res: dict, z_qsos, prior: dict | None, params: Parameters, met
     return out
 
 
+def _finish_summaries(out: dict, res: dict, summaries, max_dlas: int) -> dict:
+    """Add the summary variables to the saved ones.  ``res`` holds Engine.process_summaries's arrays
+    (D x Q MAP indices, D x Q x D MAP pairs, Q x 5 x nz x nn planes).  ``MAP_z_dlas`` / ``MAP_log_nhis``
+    (Q x D, the names of Ho et al.'s files) are those of the DLA model with the highest posterior -- level
+    d's d pairs, the rest NaN; ``map_sample_inds`` (Q x D) keeps every level's MAP sample, 1-based with
+    0 = none like ``base_sample_inds``."""
+    grid = _summary_grid(summaries)
+    D = int(max_dlas)
+    post = np.asarray(out["model_posteriors"], dtype=np.float64)[:, 1:1 + D]
+    Q = post.shape[0]
+    level = np.argmax(np.where(np.isnan(post), -np.inf, post), axis=1) if Q else np.zeros(0, dtype=np.int64)
+    for key in ("MAP_z_dlas", "MAP_log_nhis"):
+        v = np.asarray(res[key], dtype=np.float64)
+        if v.shape != (D, Q, D):
+            raise ValueError(f"{key} must be {(D, Q, D)}")
+        out[key] = np.ascontiguousarray(v[level, np.arange(Q), :])
+    ind = np.asarray(res["map_sample_inds"])
+    if ind.shape != (D, Q):
+        raise ValueError(f"map_sample_inds must be {(D, Q)}")
+    out["map_sample_inds"] = np.ascontiguousarray(ind.T.astype(np.float64) + 1.0)
+    if grid[0] is not None:
+        out["bin_planes"] = np.asarray(res["bin_planes"], dtype=np.float64)
+        out["bin_z_edges"], out["bin_log_nhi_edges"] = grid
+    return out
+
+
 def _finish(res: dict, z_qsos, prior: dict | None, params: Parameters, metadata: dict | None,
-            max_dlas: int = 1) -> dict:
+            max_dlas: int = 1, summaries=None) -> dict:
     """process_qsos.m:122-132, 150-155, 202-232: priors, posteriors and the saved scalars."""
+    if _summary_grid(summaries) is not None:
+        return _finish_summaries(_finish(res, z_qsos, prior, params, metadata, max_dlas), res, summaries, max_dlas)
     if max_dlas > 1:
         return _finish_multi(res, z_qsos, prior, params, metadata, max_dlas)
     Q = np.asarray(z_qsos).size
@@ -198,22 +271,34 @@ def _finish(res: dict, z_qsos, prior: dict | None, params: Parameters, metadata:
 
 def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
                  params: Parameters | None = None, test_ind=None, engine: Engine | None = None,
-                 device: int = 0, metadata: dict | None = None, max_dlas: int = 1, compute=None) -> dict:
+                 device: int = 0, metadata: dict | None = None, max_dlas: int = 1, compute=None,
+                 summaries=None, save_samples: bool = True) -> dict:
     """Run the DLA search (process_qsos.m:88-232) and return the saved variables.  ``max_dlas`` > 1
     (up to 4) runs the multi-DLA search: ``log_likelihoods_dla`` / ``log_priors_dla`` /
     ``log_posteriors_dla`` become Q x D, ``model_posteriors`` Q x (1 + D), ``sample_log_likelihoods_dla``
     Q x S x D, and ``base_sample_inds`` (1-based, 0 = none; Q x S for D = 2, else Q x S x (D - 1)) and
     ``max_dlas`` are added.  ``compute(model, samples, packed, params, device, max_dlas=D)`` replaces the
-    engine (tests) and returns Engine.process / process_multi's arrays."""
+    engine (tests) and returns Engine.process / process_multi's arrays.
+
+    ``summaries`` (True, or ``dict(z_edges=..., log_nhi_edges=...)`` for the binned masses too) has the
+    engine reduce the posterior summaries on the device (Engine.process_summaries; ``samples`` must hold
+    ``log_nhi_samples``) and adds ``MAP_z_dlas`` / ``MAP_log_nhis`` (Q x D: the pairs of the DLA model with
+    the highest posterior), ``map_sample_inds`` (Q x D, 1-based, 0 = none) and, with a grid,
+    ``bin_planes`` (Q x 5 x nz x nn), ``bin_z_edges`` and ``bin_log_nhi_edges`` (catalog.py consumes
+    them).  ``save_samples=False`` runs the engine without the sample buffers: the output then has no
+    ``sample_log_likelihoods_dla`` and no ``base_sample_inds``.  A ``compute`` replacement receives
+    ``summaries=`` / ``save_samples=False`` as keywords when they are set."""
     if not 1 <= int(max_dlas) <= 4:
         raise ValueError("max_dlas must be 1..4")
     params = params or set_parameters(k=np.asarray(model["M"]).shape[1])
     packed = _select(spectra, test_ind)
     if compute is not None:
-        res = compute(model, samples, packed, params, device, **(dict(max_dlas=max_dlas) if max_dlas > 1 else {}))
+        res = compute(model, samples, packed, params, device, **_compute_kwargs(max_dlas, summaries, save_samples))
     else:
-        res = _engine_compute(model, samples, packed, params, device, engine, max_dlas)
-    out = _finish(res, packed["z_qsos"], prior, params, metadata, max_dlas)
+        res = _engine_compute(model, samples, packed, params, device, engine, max_dlas, summaries, save_samples)
+    if not save_samples:
+        res = {k: v for k, v in res.items() if k not in ("sample_log_likelihoods_dla", "base_sample_inds")}
+    out = _finish(res, packed["z_qsos"], prior, params, metadata, max_dlas, summaries)
     if test_ind is not None:
         out["test_ind"] = np.asarray(test_ind)
     return out
@@ -228,6 +313,9 @@ PROCESSED_VARIABLES = ("training_release", "training_set_name", "dla_catalog_nam
                        "p_dlas")
 # what a multi-DLA run (max_dlas > 1) saves besides; calc_cddf.py:112-115,225 reads base_sample_inds
 MULTI_DLA_VARIABLES = ("base_sample_inds", "max_dlas")
+# what a run with summaries saves besides (process_qsos(summaries=...)); catalog.py reads them
+SUMMARY_VARIABLES = ("MAP_z_dlas", "MAP_log_nhis", "map_sample_inds", "bin_planes", "bin_z_edges",
+                     "bin_log_nhi_edges")
 
 
 def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
@@ -243,10 +331,13 @@ def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
     A multi-DLA run (``max_dlas`` = D > 1) also writes MULTI_DLA_VARIABLES, and its arrays have the
     shapes ``process_qsos`` documents: h5py then sees ``sample_log_likelihoods_dla`` as (D, S, Q) --
     ``[0]`` the first DLA, ``[1]`` the second, calc_cddf.py:89-90,107 -- and ``base_sample_inds`` as
-    (S, Q) for D = 2.  The 3-D array is written in one piece (not streamed)."""
+    (S, Q) for D = 2.  The 3-D array is written in one piece (not streamed).
+
+    A run with summaries also writes the SUMMARY_VARIABLES it produced; one with ``save_samples=False``
+    has no sample array (and no ``base_sample_inds``) to write."""
     mat = {}
     multi = int(np.ravel(out.get("max_dlas", 1))[0]) > 1
-    for key in PROCESSED_VARIABLES + (MULTI_DLA_VARIABLES if multi else ()):
+    for key in PROCESSED_VARIABLES + (MULTI_DLA_VARIABLES if multi else ()) + SUMMARY_VARIABLES:
         if key not in out:
             continue
         v = out[key]
@@ -395,7 +486,8 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
                      dla_catalog_name: str, prior_ind, release: str, test_set_name: str, test_ind,
                      params: Parameters | None = None, device: int = 0, save: bool = True,
                      rank: int = 0, world: int = 1, compute=None, timings: dict | None = None,
-                     chunk_rows: int | None = None, max_dlas: int = 1) -> dict:
+                     chunk_rows: int | None = None, max_dlas: int = 1, summaries=None,
+                     save_samples: bool = True) -> dict:
     """The whole ``process_qsos`` script (process_qsos.m:1-249) on files laid out as the reference
     lays them out (set_parameters.m:79-86):
 
@@ -426,12 +518,16 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
     v7.3 file, :222-249).
     Rank 0 returns the saved scalars; other ranks their local results.
     ``max_dlas`` > 1 runs the multi-DLA search (see ``process_qsos``) on one GPU only: the sharded
-    writer is 2-D, so ``world`` > 1 raises NotImplementedError."""
+    writer is 2-D, so ``world`` > 1 raises NotImplementedError.
+    ``summaries`` / ``save_samples`` as in ``process_qsos`` (the file then holds the SUMMARY_VARIABLES and,
+    with ``save_samples=False``, no sample array), on one GPU only as well."""
     import time
     if not 1 <= int(max_dlas) <= 4:
         raise ValueError("max_dlas must be 1..4")
     if max_dlas > 1 and world > 1:
         raise NotImplementedError("max_dlas > 1 with world > 1: the sharded writer takes the 2-D sample array only")
+    if (_summary_grid(summaries) is not None or not save_samples) and world > 1:
+        raise NotImplementedError("summaries / save_samples=False with world > 1: the summaries are not gathered")
     from .matv73 import LazyArray, LazyMat, auto_chunk_rows, is_matv73, loadmat, write_chunks
     from .shard import block_lpt_shards, expected_pixels, merge_shards
     compute = compute or _engine_compute
@@ -476,12 +572,14 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
         eng = Engine(model, samples, params, device=device)
         tm["engine_create_s"] = time.perf_counter() - t_load
         try:
-            res = (eng.process_multi(packed, max_dlas, want_samples=True) if max_dlas > 1 else
-                   eng.process(packed, want_samples=True, timings=tm))
+            res = _engine_compute(model, samples, packed, params, device, eng, max_dlas, summaries, save_samples,
+                                  timings=tm)
         finally:
             eng.close()
     else:
-        res = compute(model, samples, packed, params, device, **(dict(max_dlas=max_dlas) if max_dlas > 1 else {}))
+        res = compute(model, samples, packed, params, device, **_compute_kwargs(max_dlas, summaries, save_samples))
+    if not save_samples:
+        res = {k: v for k, v in res.items() if k not in ("sample_log_likelihoods_dla", "base_sample_inds")}
     t_comp = time.perf_counter()
     tm["compute_s"] = t_comp - t_load
     meta = dict(training_release=training_release, training_set_name=training_set_name,
@@ -490,7 +588,7 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
     prior = dict(z_qsos=pz, dla_ind=pdla, z_dlas=pzd)
     path = f"{rdir}/processed_qsos_{test_set_name}.mat"
     if world == 1:
-        out = _finish(res, z_all, prior, params, meta, max_dlas)
+        out = _finish(res, z_all, prior, params, meta, max_dlas, summaries)
         out["test_ind"] = tind
         if save:
             save_processed_qsos(path, out)

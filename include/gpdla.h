@@ -243,6 +243,65 @@ int gpdla_engine_get_multi_stats(gpdla_engine* engine, gpdla_multi_stats* stats)
 int gpdla_resample_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
                        const double* u, int32_t* out_inds);
 
+/* ---- Posterior summaries ---------------------------------------------------
+ * What the catalogue (generate_ascii_catalog.m:73-80) and the population statistics (CDDF_analysis/
+ * calc_cddf.py:98, _get_z_nhi_hist :829-870) take from the sample log-likelihoods, reduced on the device
+ * so the [D][Q][S] array itself becomes optional.  Per spectrum and level d:
+ *   map_sample_inds       the smallest index attaining the maximum over the non-NaN samples (nanmax's
+ *                         first maximum), -1 if every sample is NaN; map_log_likelihoods that maximum (NaN)
+ *   map_z_dlas/_log_nhis  the d (z_DLA, log N_HI) pairs of that sample: its own, then those of its base
+ *                         chain (b1 = level d's base index of j, b2 = level d-1's base index of b1,
+ *                         ...: base_sample_inds[d-2][q][j], [d-3][q][b1], ...); z = min_z + (max_z - min_z) *
+ *                         offset with the product and the sum rounded separately.  Slots >= d are NaN; all
+ *                         are NaN when there is no MAP sample or the chain meets a -1.
+ * and for level 1, when a grid is given, the normalised masses pi_j = w_j / W, w_j = exp(l_j - max)
+ * (NaN -> 0), W = sum w_j (every pi = 0 if W is 0 or not finite), summed per bin of the grid: sample j
+ * belongs to bin (iz, in) when z_edges[iz] <= z_j < z_edges[iz+1] and log_nhi_edges[in] <= log_nhi_j <
+ * log_nhi_edges[in+1]; samples outside are dropped.  The GPDLA_SUMMARY_PLANES sums per bin are
+ *   sum pi, sum pi^2, sum N pi, sum N^2 pi, sum N^2 pi^2      (N = nhi_samples)
+ * Every output is a fixed-order reduction: repeated calls and any split into device batches agree bit for
+ * bit. */
+#define GPDLA_SUMMARY_PLANES 5
+#define GPDLA_SUMMARY_MAX_BINS 1024
+typedef struct gpdla_summary_spec {
+  const double* log_nhi_samples;     /* host [S], the engine's samples' log10 N_HI in the caller's order */
+  int32_t num_z_bins, num_nhi_bins;  /* nz, nn with nz nn <= GPDLA_SUMMARY_MAX_BINS; 0, 0 = MAP only */
+  const double* z_edges;             /* host [nz + 1], absolute redshift, finite, strictly increasing */
+  const double* log_nhi_edges;       /* host [nn + 1], likewise */
+} gpdla_summary_spec;
+
+typedef struct gpdla_summaries {
+  int32_t memory;                    /* GPDLA_MEM_HOST or GPDLA_MEM_DEVICE */
+  int32_t* map_sample_inds;          /* [D][Q] 0-based, -1 = none */
+  double* map_log_likelihoods;       /* [D][Q] */
+  double* map_z_dlas;                /* [D][Q][GPDLA_MAX_DLAS] */
+  double* map_log_nhis;              /* [D][Q][GPDLA_MAX_DLAS] */
+  double* bin_planes;                /* [Q][GPDLA_SUMMARY_PLANES][nz][nn]; NULL only when nz = nn = 0 */
+} gpdla_summaries;
+
+/* gpdla_engine_process_multi (max_dlas 1..GPDLA_MAX_DLAS, the same restrictions and the same results,
+ * bit for bit) with the summaries computed per device batch after its last level.  Here
+ * results->sample_log_likelihoods_dla and ->base_sample_inds may be NULL at no loss: the catalogue and
+ * the binned masses no longer need them.  GPDLA_EINVAL for a null spec, summaries or required array, one
+ * of nz / nn zero and the other not, more than GPDLA_SUMMARY_MAX_BINS bins, non-finite or
+ * non-increasing edges. */
+int gpdla_engine_process_summaries(gpdla_engine* engine, const gpdla_spectra* spectra,
+                                   const gpdla_multi_dla* multi, const gpdla_results_multi* results,
+                                   const gpdla_summary_spec* spec, const gpdla_summaries* summaries);
+/* Cumulative kernel time (HIP events) and count of the summary launches since create / reset_stats. */
+int gpdla_engine_get_summary_stats(gpdla_engine* engine, double* ms, int64_t* launches);
+/* The summary kernel alone, host buffers: ll [levels][rows][ld] (ld >= S), the samples in the rows'
+ * order (offset_samples, log_nhi_samples, nhi_samples, each [S]), min_z / max_z [rows], base_inds
+ * [levels - 1][rows][ld] (0-based, -1 = none; NULL when levels = 1).  spec gives the grid (its
+ * log_nhi_samples is not read here); outputs as in gpdla_summaries with D = levels, Q = rows, in host
+ * memory. */
+int gpdla_posterior_summary_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
+                                const double* offset_samples, const double* log_nhi_samples,
+                                const double* nhi_samples, const double* min_z, const double* max_z,
+                                const int32_t* base_inds, int32_t levels, const gpdla_summary_spec* spec,
+                                int32_t* map_sample_inds, double* map_log_likelihoods, double* map_z_dlas,
+                                double* map_log_nhis, double* bin_planes);
+
 /* voigt MEX replacement (voigt.c:253-304).  Host buffers.  out has n_padded - 6 values. */
 int gpdla_voigt_f64(const double* lambdas, int64_t n_padded, double z, double N,
                     int32_t num_lines, double* out);
