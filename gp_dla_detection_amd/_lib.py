@@ -109,6 +109,27 @@ class Summaries(C.Structure):
                 ("map_z_dlas", dp), ("map_log_nhis", dp), ("bin_planes", dp)]
 
 
+class Forest(C.Structure):
+    _fields_ = [("num_forest_lines", C.c_int32), ("variance_series", C.c_int32), ("mean_flux", C.c_int32),
+                ("mean_flux_tau_0", C.c_double), ("mean_flux_beta", C.c_double)]
+
+
+class SubDla(C.Structure):
+    _fields_ = [("nhi_samples", dp)]
+
+
+class ResultsSub(C.Structure):
+    _fields_ = [("memory", C.c_int32), ("log_likelihoods_lls", dp), ("sample_log_likelihoods_lls", dp),
+                ("sample_ld", C.c_int64), ("log_nhi_samples", dp), ("map_sample_inds", i32p),
+                ("map_log_likelihoods", dp), ("map_z_lls", dp), ("map_log_nhi_lls", dp)]
+
+
+class ModelStats(C.Structure):
+    _fields_ = [("forest_ms", C.c_double), ("sub_dla_ms", C.c_double), ("sub_dla_reduce_ms", C.c_double),
+                ("forest_launches", C.c_int64), ("sub_dla_launches", C.c_int64),
+                ("sub_dla_reduce_launches", C.c_int64)]
+
+
 class DlaPrior(C.Structure):
     _fields_ = [("alpha", C.c_double), ("uniform_min", C.c_double), ("uniform_max", C.c_double),
                 ("fit_min", C.c_double), ("fit_max", C.c_double), ("fit_upper", C.c_double)]
@@ -142,6 +163,12 @@ SIGNATURES = {
     "gpdla_engine_get_summary_stats": (C.c_int, [C.c_void_p, dp, i64p]),
     "gpdla_posterior_summary_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, dp, i32p,
                                               C.c_int32, C.POINTER(SummarySpec), i32p, dp, dp, dp, dp]),
+    "gpdla_engine_set_forest": (C.c_int, [C.c_void_p, C.POINTER(Forest)]),
+    "gpdla_forest_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, dp]),
+    "gpdla_engine_process_models": (C.c_int, [C.c_void_p, C.POINTER(Spectra), C.POINTER(MultiDla), C.POINTER(SubDla),
+                                              C.POINTER(ResultsMulti), C.POINTER(ResultsSub), C.POINTER(SummarySpec),
+                                              C.POINTER(Summaries)]),
+    "gpdla_engine_get_model_stats": (C.c_int, [C.c_void_p, C.POINTER(ModelStats)]),
     "gpdla_resample_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, i32p]),
     "gpdla_voigt_f64": (C.c_int, [dp, C.c_int64, C.c_double, C.c_double, C.c_int32, dp]),
     "gpdla_voigt_batch_f64": (C.c_int, [dp, C.c_int64, dp, dp, C.c_int64, C.c_int32, dp]),

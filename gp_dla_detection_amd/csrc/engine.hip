@@ -98,7 +98,8 @@ struct TimedLaunch {
   hipEvent_t start, stop;
   int kind;  // 0 prep, 1 likelihood, 2 reduce, 3 contraction (panel-GEMM paths, inside 1);
              // gpdla_engine_process_multi only: 4 resample, 5 level >= 2 sweep, 6 its log-mean-exp;
-             // 7 posterior summaries (gpdla_engine_process_summaries)
+             // 7 posterior summaries (gpdla_engine_process_summaries); 8 forest kernel; gpdla_engine_process_models
+             // only: 9 sub-DLA sweep, 10 its log-mean-exp and MAP launches
   int level; // multi-DLA level the span also counts for in gpdla_multi_stats (0: none)
 };
 
@@ -207,6 +208,20 @@ struct gpdla_engine {
   double summary_ms = 0.0;
   int64_t summary_launches = 0;
 
+  // Lyman-series forest (gpdla_engine_set_forest): applied by every process* call while set
+  bool forest_on = false;
+  gpdla_forest forest{};
+  // sub-DLA model (gpdla_engine_process_models): the call's column densities in sweep and in caller
+  // order and their log10, a batch's [nq][S] sample rows, [nq] evidences, the sweep's discarded null
+  // lane and the MAP outputs ([nq] index / value, [nq][kMaxDlas] pairs)
+  std::vector<int32_t> h_perm;       // sorted sample index -> caller's sample index (d_perm)
+  double *d_sub_nhi = nullptr, *d_sub_nhi_c = nullptr, *d_sub_lognhi = nullptr, *d_sub_sll = nullptr,
+         *d_sub_ev = nullptr, *d_sub_null = nullptr, *d_sub_mll = nullptr, *d_sub_mz = nullptr, *d_sub_mn = nullptr;
+  int32_t* d_sub_mind = nullptr;
+  size_t cap_sub_nhi = 0, cap_sub_nhi_c = 0, cap_sub_lognhi = 0, cap_sub_sll = 0, cap_sub_ev = 0, cap_sub_null = 0,
+         cap_sub_mll = 0, cap_sub_mz = 0, cap_sub_mn = 0, cap_sub_mind = 0;
+  gpdla_model_stats model_stats{};
+
   std::vector<TimedLaunch> pending;
   gpdla_stats stats{};
 };
@@ -233,6 +248,9 @@ int resolve_events(gpdla_engine* e) {
     if (t.kind == 4) { e->mstats.resample_ms += ms; e->mstats.resample_launches++; }
     if (t.kind == 6) { e->mstats.multi_reduce_ms += ms; e->mstats.multi_reduce_launches++; }
     if (t.kind == 7) { e->summary_ms += ms; e->summary_launches++; }
+    if (t.kind == 8) { e->model_stats.forest_ms += ms; e->model_stats.forest_launches++; }
+    if (t.kind == 9) { e->model_stats.sub_dla_ms += ms; e->model_stats.sub_dla_launches++; }
+    if (t.kind == 10) { e->model_stats.sub_dla_reduce_ms += ms; e->model_stats.sub_dla_reduce_launches++; }
     if (t.level >= 1 && t.level <= GPDLA_MAX_DLAS) {
       e->mstats.level_ms[t.level - 1] += ms;
       e->mstats.level_launches[t.level - 1]++;
@@ -336,7 +354,9 @@ void gpdla_engine_destroy(gpdla_engine* e) {
                   e->d_pent, e->d_ai8, e->d_off_c, e->d_nhi_c, e->d_m_sll, e->d_m_lldla, e->d_m_null,
                   e->d_m_zmin, e->d_m_zmax, e->d_m_u, e->d_m_cws, e->d_m_npix, e->d_m_base,
                   e->d_m_chain[0], e->d_m_chain[1], e->d_m_forced, e->d_s_lognhi, e->d_s_edges,
-                  e->d_s_ll, e->d_s_z, e->d_s_n, e->d_s_planes, e->d_s_ind};
+                  e->d_s_ll, e->d_s_z, e->d_s_n, e->d_s_planes, e->d_s_ind, e->d_sub_nhi, e->d_sub_nhi_c,
+                  e->d_sub_lognhi, e->d_sub_sll, e->d_sub_ev, e->d_sub_null, e->d_sub_mll, e->d_sub_mz,
+                  e->d_sub_mn, e->d_sub_mind};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (e->h_meta) (void)hipHostFree(e->h_meta);
@@ -448,6 +468,7 @@ int gpdla_engine_create(int32_t device, const gpdla_model* model, const gpdla_sa
   TRY_E(upload(e->d_off, off_sorted.data(), (size_t)e->S * 8, e->stream));
   TRY_E(upload(e->d_nhi, nhi_sorted.data(), (size_t)e->S * 8, e->stream));
   TRY_E(upload(e->d_perm, perm.data(), (size_t)e->S * 4, e->stream));
+  e->h_perm = perm;
   TRY_E(upload(e->d_lines, lines.data(), lines.size() * 8, e->stream));
   if (hipMemsetAsync(e->d_status, 0, 4, e->stream) != hipSuccess ||
       hipStreamSynchronize(e->stream) != hipSuccess)
@@ -916,7 +937,7 @@ int gpdla_engine_process(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_r
     TimedLaunch t0{}, t1{}, t2{};
     if ((rc = record_start(e, &t0, 0))) return rc;
     HIP_TRY(launch_prep(e->gemm ? 0 : e->K, pa, st));
-    if (pipe) HIP_TRY(hipEventRecord(hst.in_free, st));
+    if (pipe && !e->forest_on) HIP_TRY(hipEventRecord(hst.in_free, st));
     if (batch_i8) HIP_TRY(launch_convert_i8(e->K, ca, st));
     if (batch_gemm_i8) {
       ConvertGemmI8Args cg{};
@@ -927,6 +948,23 @@ int gpdla_engine_process(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_r
     }
     HIP_TRY(hipEventRecord(t0.stop, st));
     e->pending.push_back(t0);
+    if (e->forest_on) {  // (fused fp64 engines only: gpdla_engine_set_forest)
+      ForestArgs fa{};
+      fa.q_count = (int32_t)nq; fa.info = e->d_info; fa.offsets = e->d_meta; fa.wavelengths = wl; fa.z_qsos = zq;
+      fa.slot_cap = pa.slot_cap; fa.slot_pixel = e->d_smap;
+      fa.num_rest = e->num_rest; fa.rest = e->d_rest; fa.log_omega = e->d_logom;
+      fa.c_0 = e->c0; fa.tau_0 = e->tau0; fa.beta = e->beta;
+      fa.mf_tau_0 = e->forest.mean_flux_tau_0; fa.mf_beta = e->forest.mean_flux_beta;
+      fa.num_lines = e->forest.num_forest_lines;
+      fa.variance_series = e->forest.variance_series != 0; fa.mean_flux = e->forest.mean_flux != 0;
+      fa.panel = e->d_panel;
+      TimedLaunch t8{};
+      if ((rc = record_start(e, &t8, 8))) return rc;
+      HIP_TRY(launch_forest(e->K, fa, st));
+      HIP_TRY(hipEventRecord(t8.stop, st));
+      e->pending.push_back(t8);
+      if (pipe) HIP_TRY(hipEventRecord(hst.in_free, st));  // the forest kernel reads the wavelengths too
+    }
     if ((rc = record_start(e, &t1, 1))) return rc;
     if (batch_i8) {
       HIP_TRY(launch_likelihood_i8(e->K, li, st));
@@ -1017,6 +1055,7 @@ int gpdla_engine_reset_stats(gpdla_engine* e) {
   e->mstats = gpdla_multi_stats{};
   e->summary_ms = 0.0;
   e->summary_launches = 0;
+  e->model_stats = gpdla_model_stats{};
   return GPDLA_OK;
 }
 
@@ -1081,10 +1120,31 @@ static int validate_summary_grid(const gpdla_summary_spec* spec) {
 
 // gpdla_engine_process_multi, and with spec / sums gpdla_engine_process_summaries: the summary kernel
 // runs per batch after the last level, on the level workspaces the batch leaves on the device
+// With sub / rsub (gpdla_engine_process_models) the sub-DLA sweep runs per batch after its level 1: the
+// level-1 likelihood launch again with the sub-DLA column densities, into workspaces of its own.
 static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
                               const gpdla_results_multi* res, const gpdla_summary_spec* spec,
-                              const gpdla_summaries* sums) {
+                              const gpdla_summaries* sums, const gpdla_sub_dla* sub = nullptr,
+                              const gpdla_results_sub* rsub = nullptr) {
   if (!e || !sp || !mu || !res) return set_error(GPDLA_EINVAL, "null argument");
+  bool sub_map = false;
+  if (sub) {
+    if (!rsub || !rsub->log_likelihoods_lls) return set_error(GPDLA_EINVAL, "null sub-DLA result array");
+    if (rsub->memory != GPDLA_MEM_HOST && rsub->memory != GPDLA_MEM_DEVICE)
+      return set_error(GPDLA_EINVAL, "results_sub memory=%d", rsub->memory);
+    if (!sub->nhi_samples) return set_error(GPDLA_EINVAL, "null sub-DLA nhi_samples");
+    for (int64_t i = 0; i < e->S; ++i)
+      if (!(sub->nhi_samples[i] > 0.0 && sub->nhi_samples[i] < INFINITY))
+        return set_error(GPDLA_EINVAL, "sub-DLA nhi_samples[%lld] = %g: column densities must be finite and > 0",
+                         (long long)i, sub->nhi_samples[i]);
+    if (rsub->sample_log_likelihoods_lls && rsub->sample_ld < e->S)
+      return set_error(GPDLA_EINVAL, "sub-DLA sample_ld (%lld) < num_samples (%lld)", (long long)rsub->sample_ld,
+                       (long long)e->S);
+    if (e->gemm || e->i8)
+      return set_error(GPDLA_EUNSUPPORTED, "the sub-DLA model needs the fused fp64 path (this engine runs a panel-GEMM or int8 path)");
+    sub_map = spec && (rsub->map_sample_inds || rsub->map_log_likelihoods || rsub->map_z_lls || rsub->map_log_nhi_lls);
+    if (sub_map && !rsub->log_nhi_samples) return set_error(GPDLA_EINVAL, "sub-DLA MAP outputs need log_nhi_samples");
+  }
   if (spec) {
     if (!sums) return set_error(GPDLA_EINVAL, "null argument");
     int rcv = validate_summary_grid(spec);
@@ -1126,6 +1186,21 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
   int rc;
   if ((D > 1 || spec) && (rc = multi_caller_samples(e))) return rc;
   hipStream_t st = e->stream;
+  if (sub) {  // the column densities in the sweep's (ascending-offset) order, as the engine's own are kept
+    const size_t Ss = (size_t)S;
+    std::vector<double> sorted(Ss);
+    for (size_t i = 0; i < Ss; ++i) sorted[i] = sub->nhi_samples[e->h_perm[i]];
+    if ((rc = grow(&e->d_sub_nhi, &e->cap_sub_nhi, Ss))) return rc;
+    // (pageable host memory: the copy has left `sorted` when the call returns)
+    HIP_TRY(hipMemcpyAsync(e->d_sub_nhi, sorted.data(), Ss * 8, hipMemcpyHostToDevice, st));
+    if (sub_map) {
+      if ((rc = grow(&e->d_sub_nhi_c, &e->cap_sub_nhi_c, Ss))) return rc;
+      if ((rc = grow(&e->d_sub_lognhi, &e->cap_sub_lognhi, Ss))) return rc;
+      HIP_TRY(hipMemcpyAsync(e->d_sub_nhi_c, sub->nhi_samples, Ss * 8, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(e->d_sub_lognhi, rsub->log_nhi_samples, Ss * 8, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+  }
   const int nzb = spec ? spec->num_z_bins : 0, nnb = spec ? spec->num_nhi_bins : 0;
   const size_t nbins = (size_t)nzb * nnb;
   if (spec) {
@@ -1170,10 +1245,10 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
       }
     }
     // level 1: the single-DLA engine itself, into the level workspaces
-    gpdla_spectra sub = *sp;
-    sub.num_spectra = nq;
-    sub.offsets = sp->offsets + q0;
-    sub.z_qsos = sp->z_qsos + q0;
+    gpdla_spectra bsp = *sp;
+    bsp.num_spectra = nq;
+    bsp.offsets = sp->offsets + q0;
+    bsp.z_qsos = sp->z_qsos + q0;
     gpdla_results r1{};
     r1.memory = GPDLA_MEM_DEVICE;
     r1.log_likelihoods_no_dla = e->d_m_null;
@@ -1182,9 +1257,61 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
     r1.log_likelihoods_dla = e->d_m_lldla;
     r1.min_z_dlas = e->d_m_zmin; r1.max_z_dlas = e->d_m_zmax; r1.num_pixels = e->d_m_npix;
     const size_t p0 = e->pending.size();
-    if ((rc = gpdla_engine_process(e, &sub, &r1)) < 0) return rc;
+    if ((rc = gpdla_engine_process(e, &bsp, &r1)) < 0) return rc;
     for (size_t i = p0; i < e->pending.size(); ++i)
       if (e->pending[i].kind == 1) e->pending[i].level = 1;
+
+    if (sub) {
+      // the sub-DLA sweep on the batch's resident panel: likelihood_kernel with the sub-DLA column
+      // densities; its null lane goes to a workspace nobody reads, and nothing is added to gpdla_stats
+      if ((rc = grow(&e->d_sub_sll, &e->cap_sub_sll, plane))) return rc;
+      if ((rc = grow(&e->d_sub_ev, &e->cap_sub_ev, (size_t)nq))) return rc;
+      if ((rc = grow(&e->d_sub_null, &e->cap_sub_null, (size_t)nq))) return rc;
+      LikelihoodArgs la{};
+      la.q_count = (int32_t)nq; la.info = e->d_info; la.panel = e->d_panel; la.lam_pad = e->d_lam;
+      la.offsets = e->d_off; la.nhi = e->d_sub_nhi; la.perm = e->d_perm; la.S = S;
+      la.num_lines = e->params.num_lines; la.lines = make_line_args(e->d_lines);
+      la.sample_ll = e->d_sub_sll; la.ld = S; la.ll_null = e->d_sub_null; la.status = e->d_status;
+      TimedLaunch t9{}, t10{};
+      if ((rc = record_start(e, &t9, 9))) return rc;
+      HIP_TRY(launch_likelihood(e->K, la, st));
+      HIP_TRY(hipEventRecord(t9.stop, st));
+      e->pending.push_back(t9);
+      ReduceArgs ra{};
+      ra.q_count = (int32_t)nq; ra.info = e->d_info; ra.sample_ll = e->d_sub_sll; ra.ld = S; ra.S = S;
+      ra.ll_dla = e->d_sub_ev;
+      if ((rc = record_start(e, &t10, 10))) return rc;
+      HIP_TRY(launch_reduce(ra, st));
+      if (sub_map) {
+        if ((rc = grow(&e->d_sub_mind, &e->cap_sub_mind, (size_t)nq))) return rc;
+        if ((rc = grow(&e->d_sub_mll, &e->cap_sub_mll, (size_t)nq))) return rc;
+        if ((rc = grow(&e->d_sub_mz, &e->cap_sub_mz, (size_t)nq * kMaxDlas))) return rc;
+        if ((rc = grow(&e->d_sub_mn, &e->cap_sub_mn, (size_t)nq * kMaxDlas))) return rc;
+        SummaryArgs sa{};
+        sa.rows = (int32_t)nq; sa.levels = 1; sa.ll = e->d_sub_sll; sa.ld = S; sa.S = S;
+        sa.base = nullptr; sa.ld_base = S;
+        sa.offset = e->d_off_c; sa.log_nhi = e->d_sub_lognhi; sa.nhi = e->d_sub_nhi_c;
+        sa.zmin = e->d_m_zmin; sa.zmax = e->d_m_zmax;
+        sa.map_ind = e->d_sub_mind; sa.map_ll = e->d_sub_mll; sa.map_z = e->d_sub_mz; sa.map_n = e->d_sub_mn;
+        HIP_TRY(launch_posterior_summary(sa, st));
+      }
+      HIP_TRY(hipEventRecord(t10.stop, st));
+      e->pending.push_back(t10);
+      const hipMemcpyKind sk = rsub->memory == GPDLA_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+      HIP_TRY(hipMemcpyAsync(rsub->log_likelihoods_lls + q0, e->d_sub_ev, nq * 8, sk, st));
+      if (rsub->sample_log_likelihoods_lls)
+        HIP_TRY(hipMemcpy2DAsync(rsub->sample_log_likelihoods_lls + q0 * rsub->sample_ld, rsub->sample_ld * 8,
+                                 e->d_sub_sll, S * 8, S * 8, nq, sk, st));
+      if (sub_map) {
+        if (rsub->map_sample_inds) HIP_TRY(hipMemcpyAsync(rsub->map_sample_inds + q0, e->d_sub_mind, nq * 4, sk, st));
+        if (rsub->map_log_likelihoods) HIP_TRY(hipMemcpyAsync(rsub->map_log_likelihoods + q0, e->d_sub_mll, nq * 8, sk, st));
+        // the first of each row's kMaxDlas pairs (levels = 1)
+        if (rsub->map_z_lls)
+          HIP_TRY(hipMemcpy2DAsync(rsub->map_z_lls + q0, 8, e->d_sub_mz, kMaxDlas * 8, 8, nq, sk, st));
+        if (rsub->map_log_nhi_lls)
+          HIP_TRY(hipMemcpy2DAsync(rsub->map_log_nhi_lls + q0, 8, e->d_sub_mn, kMaxDlas * 8, 8, nq, sk, st));
+      }
+    }
 
     for (int d = 2; d <= D; ++d) {
       int32_t* chain_prev = e->d_m_chain[d & 1];        // built at level d - 1 (unused at d = 2)
@@ -1288,6 +1415,80 @@ int gpdla_engine_process_summaries(gpdla_engine* e, const gpdla_spectra* sp, con
                                    const gpdla_summaries* sums) {
   if (!spec || !sums) return set_error(GPDLA_EINVAL, "null argument");
   return process_multi_impl(e, sp, mu, res, spec, sums);
+}
+
+// ---------------------------------------------------------------------------------------------
+// sub-DLA model and Lyman-series forest (include/gpdla.h; kernels in forest.hip)
+// ---------------------------------------------------------------------------------------------
+int gpdla_engine_process_models(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
+                                const gpdla_sub_dla* sub, const gpdla_results_multi* res,
+                                const gpdla_results_sub* rsub, const gpdla_summary_spec* spec,
+                                const gpdla_summaries* sums) {
+  if (spec && !sums) return set_error(GPDLA_EINVAL, "null argument");
+  if (sub && !rsub) return set_error(GPDLA_EINVAL, "null sub-DLA results");
+  return process_multi_impl(e, sp, mu, res, spec, spec ? sums : nullptr, sub, sub ? rsub : nullptr);
+}
+
+int gpdla_engine_set_forest(gpdla_engine* e, const gpdla_forest* f) {
+  if (!e) return set_error(GPDLA_EINVAL, "null engine");
+  if (!f) {
+    e->forest_on = false;
+    e->forest = gpdla_forest{};
+    return GPDLA_OK;
+  }
+  if (f->num_forest_lines < 1 || f->num_forest_lines > kMaxLines)
+    return set_error(GPDLA_EINVAL, "num_forest_lines=%d outside [1, %d]", f->num_forest_lines, kMaxLines);
+  if (!(f->mean_flux_tau_0 >= 0.0 && f->mean_flux_tau_0 < INFINITY))
+    return set_error(GPDLA_EINVAL, "mean_flux_tau_0 = %g: must be finite and >= 0", f->mean_flux_tau_0);
+  if (!std::isfinite(f->mean_flux_beta)) return set_error(GPDLA_EINVAL, "mean_flux_beta = %g: must be finite", f->mean_flux_beta);
+  if (e->gemm || e->i8)
+    return set_error(GPDLA_EUNSUPPORTED, "the forest needs the fused fp64 path (this engine runs a panel-GEMM or int8 path)");
+  e->forest = *f;
+  e->forest_on = f->variance_series != 0 || f->mean_flux != 0;
+  return GPDLA_OK;
+}
+
+int gpdla_engine_get_model_stats(gpdla_engine* e, gpdla_model_stats* s) {
+  if (!e || !s) return set_error(GPDLA_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  int rc = resolve_events(e);
+  if (rc) return rc;
+  *s = e->model_stats;
+  return GPDLA_OK;
+}
+
+int gpdla_forest_f64(int32_t device, const double* wavelengths, int64_t n, double z_qso, double tau_0,
+                     double beta, int32_t num_forest_lines, double* out) {
+  if (!wavelengths || !out || n < 0) return set_error(GPDLA_EINVAL, "null argument or n < 0");
+  if (num_forest_lines < 1 || num_forest_lines > kMaxLines)
+    return set_error(GPDLA_EINVAL, "num_forest_lines=%d outside [1, %d]", num_forest_lines, kMaxLines);
+  if (!(tau_0 >= 0.0 && tau_0 < INFINITY) || !std::isfinite(beta) || !std::isfinite(z_qso))
+    return set_error(GPDLA_EINVAL, "tau_0 = %g, beta = %g, z_qso = %g: must be finite, tau_0 >= 0", tau_0, beta, z_qso);
+  int rc = check_device(device);
+  if (rc) return rc;
+  if (n == 0) return GPDLA_OK;
+  HIP_TRY(hipSetDevice(device));
+  double *d_wl = nullptr, *d_out = nullptr;
+  auto done = [&](int code) {
+    if (d_wl) (void)hipFree(d_wl);
+    if (d_out) (void)hipFree(d_out);
+    return code;
+  };
+#define TRY_F(expr)                                                                                                   \
+  do {                                                                                                                \
+    hipError_t e_ = (expr);                                                                                           \
+    if (e_ != hipSuccess)                                                                                             \
+      return done(set_error(e_ == hipErrorOutOfMemory ? GPDLA_ENOMEM : GPDLA_EDEVICE, "forest: %s failed: %s", #expr, \
+                            hipGetErrorString(e_)));                                                                  \
+  } while (0)
+  TRY_F(hipMalloc((void**)&d_wl, (size_t)n * 8));
+  TRY_F(hipMalloc((void**)&d_out, (size_t)n * 8));
+  TRY_F(hipMemcpy(d_wl, wavelengths, (size_t)n * 8, hipMemcpyHostToDevice));
+  TRY_F(launch_forest_f64(d_wl, n, z_qso, tau_0, beta, num_forest_lines, d_out, nullptr));
+  TRY_F(hipMemcpy(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost));
+#undef TRY_F
+  return done(GPDLA_OK);
 }
 
 int gpdla_engine_get_summary_stats(gpdla_engine* e, double* ms, int64_t* launches) {

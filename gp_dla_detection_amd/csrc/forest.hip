@@ -1,0 +1,125 @@
+// Lyman-series forest of the null model (Ho, Bird & Garnett 2020,
+// arXiv:2003.11036): the effective optical depth of the series at a pixel,
+//   sum_{i=1..L} tau_0 c_i (1 + z_i)^beta [z_i <= z_QSO],  z_i = (lambda - lambda_i) / lambda_i,
+// with lambda_i = kTransitionWavelengths[i-1] 1e8 Angstrom and c_i = kLeadingConstants[i-1] /
+// kLeadingConstants[0] (= f_i lambda_i / (f_1 lambda_1)), summed in line order.  forest_kernel runs
+// between prep_kernel and the likelihood sweep and rewrites the kMu / kOmega2 words of the valid
+// slots of the fused layout; forest_f64_kernel is the same sum on a plain wavelength array.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "device_common.h"
+#include "internal.h"
+
+namespace gpdla {
+
+namespace {
+
+// lambda_i (Angstrom) and c_i into LDS: one multiplication / one division each, correctly rounded,
+// i.e. the doubles a host restatement gets from the same two tables
+__device__ inline void forest_tables(double* s_lam, double* s_c) {
+  if (threadIdx.x < kMaxLines) {
+    s_lam[threadIdx.x] = kTransitionWavelengths[threadIdx.x] * 1e8;
+    s_c[threadIdx.x] = kLeadingConstants[threadIdx.x] / kLeadingConstants[0];
+  }
+  __syncthreads();
+}
+
+// sum_i t_i(tau_0, beta) at observed wavelength lam.  The comparison and 1 + z_i are evaluated as
+// written (no contraction): a pixel one ulp either side of a line's edge must take the side the
+// model's definition gives it.
+__device__ inline double forest_tau(double lam, double z_qso, double tau_0, double beta, int L,
+                                    const double* s_lam, const double* s_c) {
+#pragma clang fp contract(off)
+  double sum = 0.0;
+  for (int i = 0; i < L; ++i) {
+    const double li = s_lam[i];
+    const double zi = (lam - li) / li;
+    if (zi <= z_qso) {
+      const double base = 1.0 + zi;
+      sum += tau_0 * s_c[i] * pow(base, beta);
+    }
+  }
+  return sum;
+}
+
+// One thread per slot; gridDim.y blocks share a spectrum's slots.  Slot j holds segment j / Ls, step
+// j % Ls, i.e. pixel-order position gg L + t (prep_kernel pass 3a); masked, padding and round-up
+// slots have no pixel and keep their neutral words.
+__global__ __launch_bounds__(256) void forest_kernel(ForestArgs a) {
+  __shared__ double s_lam[kMaxLines], s_c[kMaxLines];
+  forest_tables(s_lam, s_c);
+  const int q = blockIdx.x;
+  const SpecInfo inf = a.info[q];
+  if (inf.J == 0) return;
+  const int64_t pb = a.offsets[q];
+  const double* wl = a.wavelengths + pb;
+  const double z = a.z_qsos[q];
+  const int64_t sb = inf.slot_base, cap = a.slot_cap[q];
+  const int32_t* smap = a.slot_pixel + sb;
+  const int L = inf.L, J = inf.J;
+  const int Ls = L > 0 ? ((L + kChunkSteps - 1) / kChunkSteps) * kChunkSteps : kChunkSteps;
+  const double fv = ldexp(1.0, inf.scale_e);
+  for (int64_t j = threadIdx.x + 256 * (int64_t)blockIdx.y; j < cap; j += 256 * (int64_t)gridDim.y) {
+    const int gg = (int)(j / Ls), t = (int)(j - (int64_t)gg * Ls);
+    const int pos = (gg < 4 && t < L) ? gg * L + t : -1;
+    const int pix = (pos >= 0 && pos < J) ? smap[pos] : -1;
+    if (pix < 0) continue;
+    // the pixel's own wavelength: in reference mode the slot's kLam word is the pos-th in-range
+    // wavelength (the profile's), while its flux and model are the pos-th unmasked pixel's
+    const double lam = wl[pix];
+    double* row = a.panel + (sb + j) * a.row;
+    if (a.variance_series) {
+      const double rest = lam / (1 + z);
+      const int gi = interp_index(a.rest, a.num_rest, rest);
+      const double lom = interp_eval(a.rest, a.log_omega, a.num_rest, gi, rest);
+      const double tau = forest_tau(lam, z, a.tau_0, a.beta, a.num_lines, s_lam, s_c);
+      double om2 = exp(2 * lom);
+      const double sf = 1 - exp(-tau) + a.c_0;
+      om2 = om2 * (sf * sf);
+      row[a.w_omega2] = om2 * fv;
+    }
+    if (a.mean_flux) {
+      const double tau = forest_tau(lam, z, a.mf_tau_0, a.mf_beta, a.num_lines, s_lam, s_c);
+      row[a.w_mu] = row[a.w_mu] * exp(-tau);  // (mu 2^(E/2)) e = (mu e) 2^(E/2): the scaling is exact
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void forest_f64_kernel(const double* __restrict__ wl, int64_t n, double z_qso,
+                                                         double tau_0, double beta, int32_t L,
+                                                         double* __restrict__ out) {
+  __shared__ double s_lam[kMaxLines], s_c[kMaxLines];
+  forest_tables(s_lam, s_c);
+  const int64_t i = threadIdx.x + 256 * (int64_t)blockIdx.x;
+  if (i < n) out[i] = forest_tau(wl[i], z_qso, tau_0, beta, L, s_lam, s_c);
+}
+
+}  // namespace
+
+#define GPDLA_FOR_EACH_RANK(X) X(4) X(8) X(10) X(12) X(16) X(20) X(24)
+
+hipError_t launch_forest(int K, ForestArgs a, hipStream_t s) {
+  a.row = 0;
+#define X(k) if (K == k) { a.row = Layout<k>::kRow; a.w_mu = Layout<k>::kMu; a.w_omega2 = Layout<k>::kOmega2; }
+  GPDLA_FOR_EACH_RANK(X)
+#undef X
+  if (a.row == 0 || a.num_lines < 1 || a.num_lines > kMaxLines) return hipErrorInvalidValue;
+  if (a.q_count < 1) return hipSuccess;
+  hipLaunchKernelGGL(forest_kernel, dim3((unsigned)a.q_count, 4), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_forest_f64(const double* wl, int64_t n, double z_qso, double tau_0, double beta, int32_t L,
+                             double* out, hipStream_t s) {
+  if (L < 1 || L > kMaxLines) return hipErrorInvalidValue;
+  if (n < 1) return hipSuccess;
+  const int64_t nb = (n + 255) / 256;
+  if (nb > INT32_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(forest_f64_kernel, dim3((unsigned)nb), dim3(256), 0, s, wl, n, z_qso, tau_0, beta, L, out);
+  return hipGetLastError();
+}
+
+}  // namespace gpdla

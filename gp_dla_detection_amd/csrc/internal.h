@@ -535,6 +535,31 @@ struct SummaryArgs {
 };
 hipError_t launch_posterior_summary(const SummaryArgs& a, hipStream_t s);
 
+// ---- Lyman-series forest (forest.hip): rewrites the kMu / kOmega2 words of a batch's valid slots
+// between prep_kernel and the sweeps (fused fp64 layout only)
+struct ForestArgs {
+  int32_t q_count;
+  const SpecInfo* info;          // written by prep_kernel
+  const int64_t* offsets;        // device [q_count + 1], relative to wavelengths (PrepArgs::offsets)
+  const double* wavelengths;
+  const double* z_qsos;          // device [q_count]
+  const int64_t* slot_cap;       // device [q_count]
+  const int32_t* slot_pixel;     // prep_kernel's slot -> pixel map
+  int32_t num_rest;
+  const double* rest;
+  const double* log_omega;
+  double c_0, tau_0, beta;       // the model's (variance series)
+  double mf_tau_0, mf_beta;      // mean flux
+  int32_t num_lines;             // L, 1..kMaxLines
+  int32_t variance_series, mean_flux;
+  int32_t row, w_mu, w_omega2;   // set by launch_forest: Layout<K>::kRow, kMu, kOmega2
+  double* panel;
+};
+hipError_t launch_forest(int K, ForestArgs a, hipStream_t s);
+// sum_i t_i(tau_0, beta) at n wavelengths (device buffers), the device function forest_kernel calls
+hipError_t launch_forest_f64(const double* wl, int64_t n, double z_qso, double tau_0, double beta, int32_t L,
+                             double* out, hipStream_t s);
+
 // host-side table fitting (faddeeva_host.cpp)
 void fit_core_table(int line, double* core);
 void fit_wing_line(int line, double* wing);

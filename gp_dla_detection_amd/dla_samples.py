@@ -76,6 +76,60 @@ def generate_dla_samples(log_nhis, num_dla_samples: int = P.NUM_DLA_SAMPLES, alp
                 fit=dict(coeffs=fit[:3].copy(), Z=float(fit[3]), bandwidth=float(fit[4])))
 
 
+SUB_DLA_MIN_LOG_NHI = 19.5  # the sub-DLA model's column-density range (Ho, Bird & Garnett 2020)
+SUB_DLA_MAX_LOG_NHI = 20.0
+
+
+def sub_dla_samples(num: int, lo: float = SUB_DLA_MIN_LOG_NHI, hi: float = SUB_DLA_MAX_LOG_NHI, u=None,
+                    device: int = 0) -> dict:
+    """Column densities of the sub-DLA model: log N_j = lo + (hi - lo) u_j, uniform over [lo, hi].  ``u``
+    defaults to the second coordinate of ``halton_rr2(num, bases=(2, 3))`` -- the point set the DLA samples
+    come from, so with the engine's own offsets the (z, N) pairs stay a 2-D low-discrepancy set (that default
+    runs on the device).  Returns ``lls_log_nhi_samples`` and ``lls_nhi_samples`` (10 .^ log)."""
+    if not hi > lo:
+        raise ValueError("sub-DLA range needs hi > lo")
+    uu = halton_rr2(num, bases=(2, 3), device=device)[:, 1] if u is None else np.asarray(u, dtype=np.float64).ravel()
+    if uu.size != num or np.any(~((uu >= 0) & (uu <= 1))):
+        raise ValueError("u must hold num values in [0, 1]")
+    log_nhi = lo + (hi - lo) * uu
+    return dict(lls_log_nhi_samples=log_nhi, lls_nhi_samples=10.0 ** log_nhi)
+
+
+def _fit_integral(coeffs, lo: float, hi: float, ref: float) -> float:
+    """integral over [lo, hi] of exp(c2 x^2 + c1 x + c0) up to a factor that depends on the coefficients and
+    ``ref`` only (it cancels in a ratio of two such integrals): the erf difference for a concave quadratic
+    (as the sampler's normaliser Z), taken on erfc in a tail so it does not cancel; otherwise Gauss-Legendre
+    of exp(p(x) - p(ref))."""
+    import math
+    c2, c1, c0 = (float(c) for c in coeffs)
+    if c2 < 0:
+        s = math.sqrt(-c2)
+        m = -c1 / (2 * c2)
+        a, b = s * (lo - m), s * (hi - m)
+        if a > 0:
+            return math.erfc(a) - math.erfc(b)
+        if b < 0:
+            return math.erfc(-b) - math.erfc(-a)
+        return math.erf(b) - math.erf(a)
+    x, w = np.polynomial.legendre.leggauss(64)
+    t = 0.5 * (hi - lo) * x + 0.5 * (hi + lo)
+    return float(0.5 * (hi - lo) * np.sum(w * np.exp(np.polyval([c2, c1, c0], t) - np.polyval([c2, c1, c0], ref))))
+
+
+def sub_dla_prior_ratio(fit, lo: float = SUB_DLA_MIN_LOG_NHI, hi: float = SUB_DLA_MAX_LOG_NHI,
+                        dla_lo: float = P.UNIFORM_MIN_LOG_NHI, dla_hi: float = P.UNIFORM_MAX_LOG_NHI) -> float:
+    """r = Z_sub / Z_DLA with Z_sub = int_lo^hi g and Z_DLA = int_dla_lo^dla_hi g, g(x) = exp(polyval(coeffs, x))
+    the column-density fit ``generate_dla_samples`` returns in ``fit`` (the dict, or its three coefficients,
+    highest power first).  Pr(sub-DLA) = r Pr(DLA)."""
+    coeffs = fit["coeffs"] if isinstance(fit, dict) else fit
+    coeffs = np.asarray(coeffs, dtype=np.float64).ravel()
+    if coeffs.size != 3 or not np.all(np.isfinite(coeffs)):
+        raise ValueError("fit must hold three finite polynomial coefficients")
+    if not (hi > lo and dla_hi > dla_lo):
+        raise ValueError("integration ranges must be increasing")
+    return _fit_integral(coeffs, lo, hi, dla_lo) / _fit_integral(coeffs, dla_lo, dla_hi, dla_lo)
+
+
 def run_generate_dla_samples(base_directory: str, training_release: str, dla_catalog_name: str,
                              num_dla_samples: int = P.NUM_DLA_SAMPLES, device: int = 0) -> dict:
     """The script on files: reads <base>/<training_release>/processed/catalog.mat (log_nhis as a

@@ -190,8 +190,10 @@ class Engine:
         return dict(summary_ms=ms.value, summary_launches=n.value)
 
     def _run_multi(self, packed, max_dlas, resample_uniforms, base_sample_inds, want_samples, min_z_separation,
-                   occam_log_penalty, raise_numeric, memory, summary) -> dict:
-        """process_multi / process_summaries: ``summary`` is None or the samples' log N_HI and the grid."""
+                   occam_log_penalty, raise_numeric, memory, summary, sub=None, models=False) -> dict:
+        """process_multi / process_summaries / process_models: ``summary`` is None or the samples' log N_HI
+        and the grid; ``sub`` None or the sub-DLA column densities (``nhi``) and, for the MAP outputs, their
+        log10 (``log_nhi``); ``models`` routes the call through gpdla_engine_process_models."""
         D, S = int(max_dlas), self.num_samples
         offsets = np.ascontiguousarray(packed["offsets"], dtype=np.int64)
         Q = offsets.size - 1
@@ -238,7 +240,32 @@ class Engine:
             if ez is not None:
                 sout["bin_planes"] = np.zeros((Q, L.SUMMARY_PLANES, max(nz, 0), max(nn, 0)))
 
-        def call(sp, rs, sm):
+        subs, subout = None, {}
+        if sub is not None:
+            subs = L.SubDla(nhi_samples=L.ptr(sub["nhi"]))
+            subout = dict(log_likelihoods_lls=np.full(Q, np.nan))
+            if want_samples:
+                subout["sample_log_likelihoods_lls"] = np.full((Q, S), np.nan)
+            if spec is not None and sub.get("log_nhi") is not None:
+                subout.update(map_sample_ind_lls=np.full(Q, -1, dtype=np.int32), map_log_likelihood_lls=np.full(Q, np.nan),
+                              MAP_z_lls=np.full(Q, np.nan), MAP_log_nhi_lls=np.full(Q, np.nan))
+
+        def results_sub(mem, get):
+            if sub is None:
+                return None
+            return L.ResultsSub(memory=mem, log_likelihoods_lls=get("log_likelihoods_lls"),
+                                sample_log_likelihoods_lls=get("sample_log_likelihoods_lls"), sample_ld=S,
+                                log_nhi_samples=L.ptr(sub.get("log_nhi")),
+                                map_sample_inds=get("map_sample_ind_lls", C.c_int32),
+                                map_log_likelihoods=get("map_log_likelihood_lls"), map_z_lls=get("MAP_z_lls"),
+                                map_log_nhi_lls=get("MAP_log_nhi_lls"))
+
+        def call(sp, rs, sm, rsub=None):
+            if models:
+                return self.lib.gpdla_engine_process_models(
+                    self._h, C.byref(sp), C.byref(md), C.byref(subs) if subs is not None else None, C.byref(rs),
+                    C.byref(rsub) if rsub is not None else None, C.byref(spec) if spec is not None else None,
+                    C.byref(sm) if sm is not None else None)
             if spec is None:
                 return self.lib.gpdla_engine_process_multi(self._h, C.byref(sp), C.byref(md), C.byref(rs))
             return self.lib.gpdla_engine_process_summaries(self._h, C.byref(sp), C.byref(md), C.byref(rs),
@@ -261,7 +288,7 @@ class Engine:
                                  map_log_likelihoods=L.ptr(sout["map_log_likelihoods"]),
                                  map_z_dlas=L.ptr(sout["map_z_dlas"]), map_log_nhis=L.ptr(sout["map_log_nhis"]),
                                  bin_planes=L.ptr(pl) if pl is not None and pl.size else None)
-            rc = call(sp, rs, sm)
+            rc = call(sp, rs, sm, results_sub(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(subout.get(k), t)))
         elif memory == "device":
             dev = {k: L.DeviceArray.from_numpy(v, self.device) for k, v in
                    dict(wl=wl, fl=fl, nv=nv, mk=mk, zq=zq).items()}
@@ -289,13 +316,16 @@ class Engine:
                 sm = L.Summaries(memory=L.MEM_DEVICE, map_sample_inds=sptr("map_sample_inds", C.c_int32),
                                  map_log_likelihoods=sptr("map_log_likelihoods"), map_z_dlas=sptr("map_z_dlas"),
                                  map_log_nhis=sptr("map_log_nhis"), bin_planes=sptr("bin_planes"))
-            rc = call(sp, rs, sm)
+            dsub = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in subout.items() if v.size}
+            rc = call(sp, rs, sm, results_sub(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dsub[k].ptr, t) if k in dsub else None))
             if rc in (L.GPDLA_OK, L.GPDLA_ENUMERIC):
                 for k, d in dout.items():
                     out[k] = d.numpy()
                 for k, d in dsum.items():
                     sout[k] = d.numpy()
-            for d in list(dev.values()) + list(dout.values()) + list(dsum.values()):
+                for k, d in dsub.items():
+                    subout[k] = d.numpy()
+            for d in list(dev.values()) + list(dout.values()) + list(dsum.values()) + list(dsub.values()):
                 d.free()
         else:
             raise ValueError("memory must be 'host' or 'device'")
@@ -309,7 +339,80 @@ class Engine:
             out["MAP_log_nhis"] = np.ascontiguousarray(sout["map_log_nhis"][:, :, :Dc])
             if "bin_planes" in sout:
                 out["bin_planes"] = sout["bin_planes"]
+        out.update(subout)
         return out
+
+    # --------------------------------------------------------------------- sub-DLA model and forest
+    def set_forest(self, forest=None, *, num_forest_lines: int = 31, variance_series: bool = True,
+                   mean_flux: bool = True, mean_flux_tau_0: float = 0.0023, mean_flux_beta: float = 3.65) -> None:
+        """The Lyman-series forest of every later ``process*`` call (gpdla_engine_set_forest).  ``forest`` is
+        None (the Lya-only null model, as before), True (the keyword defaults: 31 lines, both parts, Kim et
+        al. 2007's mean flux) or a dict of those keywords.  ``variance_series``: omega^2 sums the series
+        with the model's tau_0, beta, c_0; ``mean_flux``: mu is multiplied by exp(-sum_i tau_0 c_i (1 + z_i)^beta)
+        for every model.  Fused fp64 path only."""
+        if forest is None or forest is False:
+            L.check(self.lib.gpdla_engine_set_forest(self._h, None))
+            return
+        kw = dict(num_forest_lines=num_forest_lines, variance_series=variance_series, mean_flux=mean_flux,
+                  mean_flux_tau_0=mean_flux_tau_0, mean_flux_beta=mean_flux_beta)
+        if isinstance(forest, dict):
+            unknown = set(forest) - set(kw)
+            if unknown:
+                raise TypeError(f"unexpected forest settings {sorted(unknown)}")
+            kw.update(forest)
+        fs = L.Forest(num_forest_lines=int(kw["num_forest_lines"]), variance_series=int(bool(kw["variance_series"])),
+                      mean_flux=int(bool(kw["mean_flux"])), mean_flux_tau_0=float(kw["mean_flux_tau_0"]),
+                      mean_flux_beta=float(kw["mean_flux_beta"]))
+        L.check(self.lib.gpdla_engine_set_forest(self._h, C.byref(fs)))
+
+    def process_models(self, packed: dict, max_dlas: int = 1, sub_dla=None, log_nhi_samples=None, z_edges=None,
+                       log_nhi_edges=None, sub_dla_log_nhi=None, want_samples: bool = True, **kwargs) -> dict:
+        """``process_multi`` -- or, with ``log_nhi_samples`` (and optionally the grid), ``process_summaries`` --
+        plus the sub-DLA model (gpdla_engine_process_models).  ``sub_dla``: S column densities (cm^-2) in the
+        engine's sample order; sample j is one absorber at the engine's own z_j with that column density.
+        Adds ``log_likelihoods_lls`` (Q; log-mean-exp, any NaN -> NaN), ``sample_log_likelihoods_lls`` (Q x S,
+        with ``want_samples``) and, with summaries, ``map_sample_ind_lls`` (Q int32, -1 = none),
+        ``map_log_likelihood_lls``, ``MAP_z_lls`` and ``MAP_log_nhi_lls`` (Q; ``sub_dla_log_nhi`` defaults to
+        log10 of ``sub_dla``).  Every other array is the plain call's, bit for bit; ``sub_dla=None`` is
+        exactly that call."""
+        if (z_edges is None) != (log_nhi_edges is None):
+            raise ValueError("z_edges and log_nhi_edges go together")
+        if z_edges is not None and log_nhi_samples is None:
+            raise ValueError("a summary grid needs log_nhi_samples")
+        summary = None
+        if log_nhi_samples is not None:
+            lognhi = np.ascontiguousarray(log_nhi_samples, dtype=np.float64).ravel()
+            if lognhi.size != self.num_samples:
+                raise ValueError("one log_nhi sample per engine sample")
+            summary = dict(log_nhi=lognhi,
+                           z_edges=None if z_edges is None else np.ascontiguousarray(z_edges, dtype=np.float64).ravel(),
+                           n_edges=None if log_nhi_edges is None else np.ascontiguousarray(log_nhi_edges, dtype=np.float64).ravel())
+        sub = None
+        if sub_dla is not None:
+            nhi = np.ascontiguousarray(sub_dla, dtype=np.float64).ravel()
+            if nhi.size != self.num_samples:
+                raise ValueError("one sub-DLA column density per engine sample")
+            sub = dict(nhi=nhi, log_nhi=None)
+            if summary is not None:
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    ln = np.log10(nhi) if sub_dla_log_nhi is None else np.ascontiguousarray(sub_dla_log_nhi, dtype=np.float64).ravel()
+                if ln.size != nhi.size:
+                    raise ValueError("one sub_dla_log_nhi per sub-DLA sample")
+                sub["log_nhi"] = np.ascontiguousarray(ln)
+        order = ("resample_uniforms", "base_sample_inds", "min_z_separation", "occam_log_penalty", "raise_numeric", "memory")
+        unknown = set(kwargs) - set(order)
+        if unknown:
+            raise TypeError(f"unexpected keyword arguments {sorted(unknown)}")
+        return self._run_multi(packed, max_dlas, kwargs.get("resample_uniforms"), kwargs.get("base_sample_inds"),
+                               want_samples, kwargs.get("min_z_separation"), kwargs.get("occam_log_penalty"),
+                               kwargs.get("raise_numeric", False), kwargs.get("memory", "host"), summary, sub, True)
+
+    def model_stats(self) -> dict:
+        """gpdla_engine_get_model_stats: cumulative ms / launches of the forest kernel, the sub-DLA sweeps and
+        the sub-DLA log-mean-exp + MAP launches."""
+        s = L.ModelStats()
+        L.check(self.lib.gpdla_engine_get_model_stats(self._h, C.byref(s)))
+        return {name: getattr(s, name) for name, _ in L.ModelStats._fields_}
 
     def multi_stats(self) -> dict:
         """gpdla_engine_get_multi_stats: per-level likelihood ms / launches, resample and reduce ms."""
@@ -454,6 +557,16 @@ def posterior_summary(log_likelihoods, offset_samples, log_nhi_samples, nhi_samp
                MAP_log_nhis=np.ascontiguousarray(mn[:, :, :Lc]))
     if planes is not None:
         out["bin_planes"] = planes
+    return out
+
+
+def forest_optical_depth(wavelengths, z_qso, tau_0, beta, num_forest_lines=31, device: int = 0) -> np.ndarray:
+    """sum_i tau_0 c_i (1 + z_i)^beta [z_i <= z_qso] over the first ``num_forest_lines`` Lyman-series lines at
+    the observed ``wavelengths`` (gpdla_forest_f64: the device function the engine's forest kernel calls)."""
+    wl = np.ascontiguousarray(wavelengths, dtype=np.float64).ravel()
+    out = np.empty(wl.size)
+    L.check(L.load().gpdla_forest_f64(device, L.ptr(wl), wl.size, float(z_qso), float(tau_0), float(beta),
+                                      int(num_forest_lines), L.ptr(out)))
     return out
 
 

@@ -63,20 +63,44 @@ def model_posteriors(log_posteriors_no_dla, log_posteriors_dla):
 
 
 def multi_dla_priors(z_qsos, prior_z_qsos, prior_dla_ind, max_dlas: int = 1,
-                     prior_z_qso_increase=P.PRIOR_Z_QSO_INCREASE):
+                     prior_z_qso_increase=P.PRIOR_Z_QSO_INCREASE, sub_dla_prior_ratio=None):
     """Model priors of the multi-DLA search: with p = M / N of process_qsos.m:123-127, no DLA has prior
     1 - p, exactly d DLAs p^d - p^(d+1) for d < max_dlas and p^max_dlas for d = max_dlas (they sum to 1).
     Returns (log_priors_no_dla [Q], log_priors_dla [Q x max_dlas]); for max_dlas = 1 these are
-    ``dla_priors``'s two arrays, bit for bit."""
+    ``dla_priors``'s two arrays, bit for bit.
+
+    With ``sub_dla_prior_ratio`` r = Z_sub / Z_DLA (dla_samples.sub_dla_prior_ratio) the sub-DLA model has
+    prior r p, the DLA priors are unchanged and no absorber has 1 - p - r p (log -inf where that is <= 0);
+    a third array, log_priors_lls [Q], is returned."""
     if not 1 <= max_dlas <= 4:
         raise ValueError("max_dlas must be 1..4")
     lp_no, lp1 = dla_priors(z_qsos, prior_z_qsos, prior_dla_ind, prior_z_qso_increase)
     if max_dlas == 1:
-        return lp_no, lp1[:, None]
+        lp_dla = lp1[:, None]
+    else:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            p = np.exp(lp1)
+            cols = [np.log(p ** d - p ** (d + 1)) for d in range(1, max_dlas)] + [np.log(p ** max_dlas)]
+        lp_dla = np.stack(cols, axis=1)
+    if sub_dla_prior_ratio is None:
+        return lp_no, lp_dla
+    lp_no, lp_sub = sub_dla_priors(np.exp(lp1), sub_dla_prior_ratio)
+    return lp_no, lp_dla, lp_sub
+
+
+def sub_dla_priors(p, sub_dla_prior_ratio):
+    """(log Pr(no absorber), log Pr(sub-DLA)) for the DLA prior p: Pr(sub-DLA) = r p and Pr(none) =
+    1 - p - r p, whose log is -inf where that is <= 0."""
+    r = float(sub_dla_prior_ratio)
+    if not (np.isfinite(r) and r >= 0):
+        raise ValueError("sub_dla_prior_ratio must be finite and >= 0")
+    p = np.asarray(p, dtype=np.float64)
+    none = 1 - p - r * p
     with np.errstate(divide="ignore", invalid="ignore"):
-        p = np.exp(lp1)
-        cols = [np.log(p ** d - p ** (d + 1)) for d in range(1, max_dlas)] + [np.log(p ** max_dlas)]
-    return lp_no, np.stack(cols, axis=1)
+        lp_no = np.where(none > 0, np.log(np.where(none > 0, none, 1.0)), -np.inf)
+        lp_no = np.where(np.isnan(none), np.nan, lp_no)
+        lp_sub = np.log(r * p)
+    return lp_no, lp_sub
 
 
 def model_posteriors_multi(log_posteriors_no_dla, log_posteriors_dla):
@@ -90,6 +114,85 @@ def model_posteriors_multi(log_posteriors_no_dla, log_posteriors_dla):
     post = post / np.sum(post, axis=1, keepdims=True)
     p_no = post[:, 0]
     return post, p_no, 1 - p_no
+
+
+def model_posteriors_sub(log_posteriors_no_dla, log_posteriors_dla, log_posteriors_lls):
+    """``model_posteriors_multi`` with the sub-DLA model as one more column, placed LAST: Q x (1 + D + 1),
+    so column d still reads "exactly d DLAs" (calc_cddf.py:67).  Returns (model_posteriors, p_no_dlas, p_lls,
+    p_dlas) with p_dlas = 1 - p_no_dlas - p_lls."""
+    lp_dla = np.array(log_posteriors_dla, dtype=np.float64)
+    if lp_dla.ndim == 1:
+        lp_dla = lp_dla[:, None]
+    lp_dla[:, 1:] = np.where(np.isnan(lp_dla[:, 1:]), -np.inf, lp_dla[:, 1:])
+    lp = np.concatenate([np.asarray(log_posteriors_no_dla, dtype=np.float64)[:, None], lp_dla,
+                         np.asarray(log_posteriors_lls, dtype=np.float64)[:, None]], axis=1)
+    mx = np.max(lp, axis=1, keepdims=True)
+    post = np.exp(lp - mx)
+    post = post / np.sum(post, axis=1, keepdims=True)
+    p_no, p_lls = post[:, 0], post[:, -1]
+    return post, p_no, p_lls, 1 - p_no - p_lls
+
+
+def _sub_dla_spec(sub_dla, samples: dict, device: int = 0):
+    """``sub_dla`` of process_qsos -> None (off) or dict(nhi, log_nhi, ratio).  True takes the default samples
+    (dla_samples.sub_dla_samples: uniform over 19.5..20 on the DLA samples' own Halton points, on the device)
+    or the ``lls_log_nhi_samples`` ``samples`` holds, and the prior ratio from ``samples['sub_dla_prior_ratio']``
+    or ``samples['fit']``.  A dict gives ``lls_log_nhi_samples`` (or ``lls_nhi_samples``) and / or
+    ``sub_dla_prior_ratio`` itself."""
+    if sub_dla is None or sub_dla is False:
+        return None
+    given = {} if sub_dla is True else sub_dla
+    if not isinstance(given, dict) or set(given) - {"lls_log_nhi_samples", "lls_nhi_samples", "sub_dla_prior_ratio"}:
+        raise ValueError("sub_dla must be None, True or dict(lls_log_nhi_samples=..., sub_dla_prior_ratio=...)")
+    S = np.asarray(samples["nhi_samples"]).size
+    src = given if ("lls_log_nhi_samples" in given or "lls_nhi_samples" in given) else samples
+    if "lls_log_nhi_samples" in src:
+        log_nhi = np.ascontiguousarray(src["lls_log_nhi_samples"], dtype=np.float64).ravel()
+        nhi = (np.ascontiguousarray(src["lls_nhi_samples"], dtype=np.float64).ravel() if "lls_nhi_samples" in src
+               else 10.0 ** log_nhi)
+    elif "lls_nhi_samples" in src:
+        nhi = np.ascontiguousarray(src["lls_nhi_samples"], dtype=np.float64).ravel()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            log_nhi = np.log10(nhi)
+    else:
+        from .dla_samples import sub_dla_samples
+        d = sub_dla_samples(S, device=device)
+        log_nhi, nhi = d["lls_log_nhi_samples"], d["lls_nhi_samples"]
+    if nhi.size != S or log_nhi.size != S:
+        raise ValueError("one sub-DLA column density per DLA sample")
+    if not np.all(np.isfinite(nhi) & (nhi > 0)):
+        raise ValueError("sub-DLA column densities must be finite and > 0")
+    if "sub_dla_prior_ratio" in given:
+        ratio = float(np.ravel(given["sub_dla_prior_ratio"])[0])
+    elif "sub_dla_prior_ratio" in samples:
+        ratio = float(np.ravel(samples["sub_dla_prior_ratio"])[0])
+    elif "fit" in samples:
+        from .dla_samples import sub_dla_prior_ratio
+        ratio = sub_dla_prior_ratio(samples["fit"])
+    else:
+        raise ValueError("sub_dla needs sub_dla_prior_ratio (or samples['fit'] to derive it from)")
+    if not (np.isfinite(ratio) and ratio >= 0):
+        raise ValueError("sub_dla_prior_ratio must be finite and >= 0")
+    return dict(nhi=nhi, log_nhi=log_nhi, ratio=ratio)
+
+
+FOREST_DEFAULTS = dict(num_forest_lines=31, variance_series=True, mean_flux=True, mean_flux_tau_0=0.0023,
+                       mean_flux_beta=3.65)   # Kim et al. 2007's mean flux
+
+
+def _forest_spec(forest):
+    """``forest`` of process_qsos -> None (off) or the full settings dict (True = FOREST_DEFAULTS)."""
+    if forest is None or forest is False:
+        return None
+    given = {} if forest is True else forest
+    if not isinstance(given, dict) or set(given) - set(FOREST_DEFAULTS):
+        raise ValueError(f"forest must be None, True or a dict of {sorted(FOREST_DEFAULTS)}")
+    f = dict(FOREST_DEFAULTS, **given)
+    if not 1 <= int(f["num_forest_lines"]) <= 31:
+        raise ValueError("num_forest_lines must be 1..31")
+    if not (np.isfinite(f["mean_flux_tau_0"]) and f["mean_flux_tau_0"] >= 0 and np.isfinite(f["mean_flux_beta"])):
+        raise ValueError("mean_flux_tau_0 must be finite and >= 0, mean_flux_beta finite")
+    return f
 
 
 def _select(spectra, test_ind):
@@ -129,10 +232,15 @@ def _summary_grid(summaries):
     return np.ascontiguousarray(ez, dtype=np.float64).ravel(), np.ascontiguousarray(en, dtype=np.float64).ravel()
 
 
-def _compute_kwargs(max_dlas: int, summaries, save_samples: bool) -> dict:
+def _compute_kwargs(max_dlas: int, summaries, save_samples: bool, sub=None, forest=None) -> dict:
     """What a ``compute`` replacement is told beyond the five positional arguments: only what differs
-    from the plain single-DLA call, so existing replacements keep working."""
+    from the plain single-DLA call, so existing replacements keep working.  ``sub_dla`` is the normalised
+    dict(nhi, log_nhi, ratio), ``forest`` the full settings dict."""
     kw = {}
+    if sub is not None:
+        kw["sub_dla"] = sub
+    if forest is not None:
+        kw["forest"] = forest
     if max_dlas > 1:
         kw["max_dlas"] = max_dlas
     if _summary_grid(summaries) is not None:
@@ -144,14 +252,33 @@ def _compute_kwargs(max_dlas: int, summaries, save_samples: bool) -> dict:
 
 def _engine_compute(model: dict, samples: dict, packed: dict, params: Parameters, device: int = 0,
                     engine: Engine | None = None, max_dlas: int = 1, summaries=None, save_samples: bool = True,
-                    timings: dict | None = None) -> dict:
+                    timings: dict | None = None, sub_dla=None, forest=None) -> dict:
     """The hot path on the GPU: per-spectrum null / sample / DLA log likelihoods and z ranges; with
     ``max_dlas`` > 1 every level of the multi-DLA search (Engine.process_multi's arrays); with
     ``summaries`` the posterior summaries as well (Engine.process_summaries), the sample arrays only if
-    ``save_samples``."""
+    ``save_samples``.  ``sub_dla`` (the normalised dict of ``_sub_dla_spec``) adds the sub-DLA model's arrays
+    (Engine.process_models); ``forest`` (the settings dict) is set on the engine for this call and cleared
+    after it."""
     grid = _summary_grid(summaries)
     eng = engine or Engine(model, samples, params, device=device)
     try:
+        if forest is not None:
+            eng.set_forest(forest)
+        if sub_dla is not None:
+            if grid is not None and "log_nhi_samples" not in samples:
+                raise ValueError("summaries need samples['log_nhi_samples']")
+            res = eng.process_models(packed, max_dlas, sub_dla=sub_dla["nhi"],
+                                     log_nhi_samples=samples["log_nhi_samples"] if grid is not None else None,
+                                     z_edges=grid[0] if grid is not None else None,
+                                     log_nhi_edges=grid[1] if grid is not None else None,
+                                     sub_dla_log_nhi=sub_dla["log_nhi"], want_samples=save_samples)
+            if max_dlas == 1:   # Engine.process's shapes: no level axis, no multi-DLA variables
+                res["log_likelihoods_dla"] = res["log_likelihoods_dla"][0]
+                if "sample_log_likelihoods_dla" in res:
+                    res["sample_log_likelihoods_dla"] = res["sample_log_likelihoods_dla"][0]
+                res.pop("base_sample_inds", None)
+                res.pop("max_dlas", None)
+            return res
         if grid is not None:
             if "log_nhi_samples" not in samples:
                 raise ValueError("summaries need samples['log_nhi_samples']")
@@ -168,6 +295,8 @@ def _engine_compute(model: dict, samples: dict, packed: dict, params: Parameters
             return eng.process_multi(packed, max_dlas, want_samples=save_samples)
         return eng.process(packed, want_samples=save_samples, **(dict(timings=timings) if timings is not None else {}))
     finally:
+        if forest is not None and engine is not None:
+            eng.set_forest(None)
         if engine is None:
             eng.close()
 
@@ -236,11 +365,49 @@ def _finish_summaries(out: dict, res: dict, summaries, max_dlas: int) -> dict:
     return out
 
 
+def _finish_sub(out: dict, res: dict, z_qsos, prior: dict | None, params: Parameters, sub: dict) -> dict:
+    """The sub-DLA model on top of ``_finish``'s variables: Pr(sub-DLA) = r p, Pr(no absorber) = 1 - p - r p
+    (the DLA priors stay), ``model_posteriors`` gains a LAST column and ``p_dlas`` = 1 - p_no_dlas - p_lls."""
+    Q = np.asarray(out["log_likelihoods_no_dla"]).size
+    ll_lls = np.asarray(res["log_likelihoods_lls"], dtype=np.float64).ravel()
+    if ll_lls.size != Q:
+        raise ValueError(f"log_likelihoods_lls must have {Q} entries")
+    if prior is None:
+        p = np.full(Q, 0.5)
+    else:   # p = M / N as multi_dla_priors forms it
+        dla_ind = filter_prior_dlas(prior["z_qsos"], prior["dla_ind"], prior.get("z_dlas", [None] * len(prior["z_qsos"])))
+        p = np.exp(dla_priors(z_qsos, prior["z_qsos"], dla_ind, params.prior_z_qso_increase)[1])
+    lp_no, lp_sub = sub_dla_priors(p, sub["ratio"])
+    out["log_priors_no_dla"], out["log_priors_lls"] = lp_no, lp_sub
+    out["log_likelihoods_lls"] = ll_lls
+    out["log_posteriors_no_dla"] = lp_no + out["log_likelihoods_no_dla"]
+    out["log_posteriors_lls"] = lp_sub + ll_lls
+    post, p_no, p_lls, p_dla = model_posteriors_sub(out["log_posteriors_no_dla"], out["log_posteriors_dla"],
+                                                    out["log_posteriors_lls"])
+    out["model_posteriors"], out["p_no_dlas"], out["p_lls"], out["p_dlas"] = post, p_no, p_lls, p_dla
+    if "sample_log_likelihoods_lls" in res:
+        out["sample_log_likelihoods_lls"] = np.asarray(res["sample_log_likelihoods_lls"], dtype=np.float64)
+    out["lls_log_nhi_samples"] = sub["log_nhi"]
+    out["sub_dla_prior_ratio"] = float(sub["ratio"])
+    for key in ("MAP_z_lls", "MAP_log_nhi_lls"):
+        if key in res:
+            out[key] = np.asarray(res[key], dtype=np.float64)
+    return out
+
+
 def _finish(res: dict, z_qsos, prior: dict | None, params: Parameters, metadata: dict | None,
-            max_dlas: int = 1, summaries=None) -> dict:
+            max_dlas: int = 1, summaries=None, sub=None, forest=None) -> dict:
     """process_qsos.m:122-132, 150-155, 202-232: priors, posteriors and the saved scalars."""
+    if forest is not None:
+        out = _finish(res, z_qsos, prior, params, metadata, max_dlas, summaries, sub)
+        out.update(num_forest_lines=int(forest["num_forest_lines"]), forest_variance_series=bool(forest["variance_series"]),
+                   forest_mean_flux=bool(forest["mean_flux"]), mean_flux_tau_0=float(forest["mean_flux_tau_0"]),
+                   mean_flux_beta=float(forest["mean_flux_beta"]))
+        return out
     if _summary_grid(summaries) is not None:
-        return _finish_summaries(_finish(res, z_qsos, prior, params, metadata, max_dlas), res, summaries, max_dlas)
+        return _finish_summaries(_finish(res, z_qsos, prior, params, metadata, max_dlas, None, sub), res, summaries, max_dlas)
+    if sub is not None:
+        return _finish_sub(_finish(res, z_qsos, prior, params, metadata, max_dlas), res, z_qsos, prior, params, sub)
     if max_dlas > 1:
         return _finish_multi(res, z_qsos, prior, params, metadata, max_dlas)
     Q = np.asarray(z_qsos).size
@@ -272,7 +439,7 @@ def _finish(res: dict, z_qsos, prior: dict | None, params: Parameters, metadata:
 def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
                  params: Parameters | None = None, test_ind=None, engine: Engine | None = None,
                  device: int = 0, metadata: dict | None = None, max_dlas: int = 1, compute=None,
-                 summaries=None, save_samples: bool = True) -> dict:
+                 summaries=None, save_samples: bool = True, sub_dla=None, forest=None) -> dict:
     """Run the DLA search (process_qsos.m:88-232) and return the saved variables.  ``max_dlas`` > 1
     (up to 4) runs the multi-DLA search: ``log_likelihoods_dla`` / ``log_priors_dla`` /
     ``log_posteriors_dla`` become Q x D, ``model_posteriors`` Q x (1 + D), ``sample_log_likelihoods_dla``
@@ -287,18 +454,31 @@ def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
     ``bin_planes`` (Q x 5 x nz x nn), ``bin_z_edges`` and ``bin_log_nhi_edges`` (catalog.py consumes
     them).  ``save_samples=False`` runs the engine without the sample buffers: the output then has no
     ``sample_log_likelihoods_dla`` and no ``base_sample_inds``.  A ``compute`` replacement receives
-    ``summaries=`` / ``save_samples=False`` as keywords when they are set."""
+    ``summaries=`` / ``save_samples=False`` as keywords when they are set.
+
+    ``sub_dla`` (True, or ``dict(lls_log_nhi_samples=..., sub_dla_prior_ratio=...)``; see ``_sub_dla_spec``)
+    adds the sub-DLA model of Ho, Bird & Garnett 2020: one absorber at the engine's own z_j with column
+    density N^sub_j.  The output gains SUB_DLA_VARIABLES, ``model_posteriors`` a LAST column for it,
+    ``log_priors_no_dla`` becomes log(1 - p - r p) and ``p_dlas`` = 1 - p_no_dlas - p_lls.  ``forest`` (True, or
+    a dict overriding FOREST_DEFAULTS) makes the null model sum the Lyman series in omega^2
+    (``variance_series``) and suppress mu by the mean flux (``mean_flux``), for every model; the output
+    records FOREST_VARIABLES.  Both run on the fused fp64 path only; without them every variable is as
+    before, bit for bit.  A ``compute`` replacement receives ``sub_dla=`` (dict(nhi, log_nhi, ratio)) and
+    ``forest=`` (the full settings) when they are set."""
     if not 1 <= int(max_dlas) <= 4:
         raise ValueError("max_dlas must be 1..4")
     params = params or set_parameters(k=np.asarray(model["M"]).shape[1])
+    sub, fst = _sub_dla_spec(sub_dla, samples, device), _forest_spec(forest)
     packed = _select(spectra, test_ind)
     if compute is not None:
-        res = compute(model, samples, packed, params, device, **_compute_kwargs(max_dlas, summaries, save_samples))
+        res = compute(model, samples, packed, params, device, **_compute_kwargs(max_dlas, summaries, save_samples, sub, fst))
     else:
-        res = _engine_compute(model, samples, packed, params, device, engine, max_dlas, summaries, save_samples)
+        res = _engine_compute(model, samples, packed, params, device, engine, max_dlas, summaries, save_samples,
+                              sub_dla=sub, forest=fst)
     if not save_samples:
-        res = {k: v for k, v in res.items() if k not in ("sample_log_likelihoods_dla", "base_sample_inds")}
-    out = _finish(res, packed["z_qsos"], prior, params, metadata, max_dlas, summaries)
+        res = {k: v for k, v in res.items() if k not in ("sample_log_likelihoods_dla", "base_sample_inds",
+                                                         "sample_log_likelihoods_lls")}
+    out = _finish(res, packed["z_qsos"], prior, params, metadata, max_dlas, summaries, sub, fst)
     if test_ind is not None:
         out["test_ind"] = np.asarray(test_ind)
     return out
@@ -316,6 +496,14 @@ MULTI_DLA_VARIABLES = ("base_sample_inds", "max_dlas")
 # what a run with summaries saves besides (process_qsos(summaries=...)); catalog.py reads them
 SUMMARY_VARIABLES = ("MAP_z_dlas", "MAP_log_nhis", "map_sample_inds", "bin_planes", "bin_z_edges",
                      "bin_log_nhi_edges")
+# what a run with the sub-DLA model saves besides (process_qsos(sub_dla=...)), in the lineage's naming
+# (Ho, Bird & Garnett's files call the sub-DLA model "lls"); the MAP pair only with summaries
+SUB_DLA_VARIABLES = ("log_priors_lls", "log_likelihoods_lls", "log_posteriors_lls", "p_lls",
+                     "sample_log_likelihoods_lls", "lls_log_nhi_samples", "sub_dla_prior_ratio", "MAP_z_lls",
+                     "MAP_log_nhi_lls")
+# what a run with the Lyman-series forest records (process_qsos(forest=...))
+FOREST_VARIABLES = ("num_forest_lines", "forest_variance_series", "forest_mean_flux", "mean_flux_tau_0",
+                    "mean_flux_beta")
 
 
 def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
@@ -334,15 +522,21 @@ def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
     (S, Q) for D = 2.  The 3-D array is written in one piece (not streamed).
 
     A run with summaries also writes the SUMMARY_VARIABLES it produced; one with ``save_samples=False``
-    has no sample array (and no ``base_sample_inds``) to write."""
+    has no sample array (and no ``base_sample_inds``) to write.  A run with ``sub_dla`` writes the
+    SUB_DLA_VARIABLES (``model_posteriors`` is then Q x (1 + D + 1), the sub-DLA column last, so h5py's
+    ``model_posteriors[2]`` still reads "exactly two DLAs", calc_cddf.py:67), one with ``forest`` the
+    FOREST_VARIABLES."""
     mat = {}
     multi = int(np.ravel(out.get("max_dlas", 1))[0]) > 1
-    for key in PROCESSED_VARIABLES + (MULTI_DLA_VARIABLES if multi else ()) + SUMMARY_VARIABLES:
+    for key in (PROCESSED_VARIABLES + (MULTI_DLA_VARIABLES if multi else ()) + SUMMARY_VARIABLES + SUB_DLA_VARIABLES +
+                FOREST_VARIABLES):
         if key not in out:
             continue
         v = out[key]
         if isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool):
             v = np.float64(v)          # MATLAB numeric literals are double (num_lines = 3)
+        elif isinstance(v, (bool, np.bool_)) and key in FOREST_VARIABLES:
+            v = np.float64(v)          # the two forest flags: 0 / 1
         mat[key] = v
     if format == "v7.3":
         from .matv73 import savemat73
@@ -408,8 +602,11 @@ def load_model(path: str) -> dict:
 def load_dla_samples(path: str) -> dict:
     """process_qsos.m:37-40 (dla_samples.mat)."""
     from .matv73 import loadmat
-    d = loadmat(path, ["offset_samples", "log_nhi_samples", "nhi_samples"])
-    return {k: np.asarray(v, dtype=np.float64).ravel() for k, v in d.items()}
+    d = loadmat(path, ["offset_samples", "log_nhi_samples", "nhi_samples", "lls_log_nhi_samples", "sub_dla_prior_ratio"])
+    out = {k: np.asarray(v, dtype=np.float64).ravel() for k, v in d.items()}
+    if "sub_dla_prior_ratio" in out:
+        out["sub_dla_prior_ratio"] = float(out["sub_dla_prior_ratio"][0])
+    return out
 
 
 def save_dla_samples(path: str, samples: dict, **extra) -> None:
@@ -417,7 +614,9 @@ def save_dla_samples(path: str, samples: dict, **extra) -> None:
     (h5py sees (S, 1); calc_cddf.py:121-123 reads ``[:, 0]``)."""
     from .matv73 import savemat73
     var = {k: np.asarray(samples[k], dtype=np.float64).reshape(1, -1)
-           for k in ("offset_samples", "log_nhi_samples", "nhi_samples") if k in samples}
+           for k in ("offset_samples", "log_nhi_samples", "nhi_samples", "lls_log_nhi_samples") if k in samples}
+    if "sub_dla_prior_ratio" in samples:   # the sub-DLA model's two entries travel with the samples
+        var["sub_dla_prior_ratio"] = np.float64(samples["sub_dla_prior_ratio"])
     var.update(extra)
     savemat73(path, var)
 
@@ -487,7 +686,7 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
                      params: Parameters | None = None, device: int = 0, save: bool = True,
                      rank: int = 0, world: int = 1, compute=None, timings: dict | None = None,
                      chunk_rows: int | None = None, max_dlas: int = 1, summaries=None,
-                     save_samples: bool = True) -> dict:
+                     save_samples: bool = True, sub_dla=None, forest=None) -> dict:
     """The whole ``process_qsos`` script (process_qsos.m:1-249) on files laid out as the reference
     lays them out (set_parameters.m:79-86):
 
@@ -520,7 +719,10 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
     ``max_dlas`` > 1 runs the multi-DLA search (see ``process_qsos``) on one GPU only: the sharded
     writer is 2-D, so ``world`` > 1 raises NotImplementedError.
     ``summaries`` / ``save_samples`` as in ``process_qsos`` (the file then holds the SUMMARY_VARIABLES and,
-    with ``save_samples=False``, no sample array), on one GPU only as well."""
+    with ``save_samples=False``, no sample array), on one GPU only as well.
+    ``sub_dla`` / ``forest`` as in ``process_qsos``: ``sub_dla`` on one GPU only (``world`` > 1 raises
+    NotImplementedError: its arrays are not gathered); ``forest`` alone passes through to every rank's
+    engine."""
     import time
     if not 1 <= int(max_dlas) <= 4:
         raise ValueError("max_dlas must be 1..4")
@@ -528,6 +730,8 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
         raise NotImplementedError("max_dlas > 1 with world > 1: the sharded writer takes the 2-D sample array only")
     if (_summary_grid(summaries) is not None or not save_samples) and world > 1:
         raise NotImplementedError("summaries / save_samples=False with world > 1: the summaries are not gathered")
+    if sub_dla is not None and sub_dla is not False and world > 1:
+        raise NotImplementedError("sub_dla with world > 1: the sub-DLA arrays are not gathered")
     from .matv73 import LazyArray, LazyMat, auto_chunk_rows, is_matv73, loadmat, write_chunks
     from .shard import block_lpt_shards, expected_pixels, merge_shards
     compute = compute or _engine_compute
@@ -543,6 +747,7 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
     model = load_model(f"{tdir}/learned_qso_model_{training_set_name}.mat")
     samples = load_dla_samples(f"{tdir}/dla_samples.mat")
     params = params or set_parameters(k=np.asarray(model["M"]).shape[1])
+    sub, fst = _sub_dla_spec(sub_dla, samples, device), _forest_spec(forest)
     # the release catalogue: only what test_ind names, and z_qsos, is decoded (not its z_dlas cells)
     catalog = LazyMat(f"{rdir}/catalog.mat") if is_matv73(f"{rdir}/catalog.mat") else loadmat(f"{rdir}/catalog.mat")
     side = f"{rdir}/catalog_filter_flags.mat"
@@ -573,13 +778,14 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
         tm["engine_create_s"] = time.perf_counter() - t_load
         try:
             res = _engine_compute(model, samples, packed, params, device, eng, max_dlas, summaries, save_samples,
-                                  timings=tm)
+                                  timings=tm, sub_dla=sub, forest=fst)
         finally:
             eng.close()
     else:
-        res = compute(model, samples, packed, params, device, **_compute_kwargs(max_dlas, summaries, save_samples))
+        res = compute(model, samples, packed, params, device, **_compute_kwargs(max_dlas, summaries, save_samples, sub, fst))
     if not save_samples:
-        res = {k: v for k, v in res.items() if k not in ("sample_log_likelihoods_dla", "base_sample_inds")}
+        res = {k: v for k, v in res.items() if k not in ("sample_log_likelihoods_dla", "base_sample_inds",
+                                                         "sample_log_likelihoods_lls")}
     t_comp = time.perf_counter()
     tm["compute_s"] = t_comp - t_load
     meta = dict(training_release=training_release, training_set_name=training_set_name,
@@ -588,7 +794,7 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
     prior = dict(z_qsos=pz, dla_ind=pdla, z_dlas=pzd)
     path = f"{rdir}/processed_qsos_{test_set_name}.mat"
     if world == 1:
-        out = _finish(res, z_all, prior, params, meta, max_dlas, summaries)
+        out = _finish(res, z_all, prior, params, meta, max_dlas, summaries, sub, fst)
         out["test_ind"] = tind
         if save:
             save_processed_qsos(path, out)
@@ -605,7 +811,7 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
         warns = [f"rank {r}: {g['numeric_warning']}" for r, g in enumerate(gathered) if g.get("numeric_warning")]
         if warns:
             merged["numeric_warning"] = "; ".join(warns)
-        out = _finish(merged, z_all, prior, params, meta)
+        out = _finish(merged, z_all, prior, params, meta, forest=fst)
         out["test_ind"] = tind
         if save:   # deferred, chunked by the rows the shards were cut on
             out["sample_log_likelihoods_dla"] = LazyArray((tidx.size, S), np.float64, chunk_rows=chunk_rows)

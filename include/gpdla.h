@@ -302,6 +302,69 @@ int gpdla_posterior_summary_f64(int32_t device, const double* ll, int64_t rows, 
                                 int32_t* map_sample_inds, double* map_log_likelihoods, double* map_z_dlas,
                                 double* map_log_nhis, double* bin_planes);
 
+/* ---- Sub-DLA model and Lyman-series forest (Ho, Bird & Garnett 2020) ---------
+ * Forest.  For a pixel at observed wavelength lambda of a quasar at z_QSO and line i = 1..L
+ * (lambda_i = the i-th Lyman-series wavelength, c_i = f_i lambda_i / (f_1 lambda_1)):
+ *   z_i = (lambda - lambda_i) / lambda_i,   t_i(tau_0, beta) = tau_0 c_i (1 + z_i)^beta [z_i <= z_QSO]
+ * summed in line order.  variance_series replaces process_qsos.m:145-147 by
+ *   omega^2 = exp(2 log omega) (1 - exp(-sum_i t_i(tau_0, beta)) + c_0)^2   (the model's tau_0, beta, c_0)
+ * and mean_flux multiplies mu by exp(-sum_i t_i(mean_flux_tau_0, mean_flux_beta)) for every model (null,
+ * sub-DLA, every DLA level).  lambda is the pixel's own wavelength; masked and padding slots stay neutral.
+ * Fused fp64 path only: on an int8 or panel-GEMM engine gpdla_engine_set_forest returns
+ * GPDLA_EUNSUPPORTED (their slot scalars feed quantisation scales derived from mu, which the forest
+ * kernel does not rebuild). */
+typedef struct gpdla_forest {
+  int32_t num_forest_lines;          /* L, 1..31 */
+  int32_t variance_series;           /* nonzero: omega^2 sums the series */
+  int32_t mean_flux;                 /* nonzero: mu is suppressed by the mean flux */
+  double mean_flux_tau_0;            /* finite, >= 0 (Kim et al. 2007: 0.0023) */
+  double mean_flux_beta;             /* finite (Kim et al. 2007: 3.65) */
+} gpdla_forest;
+/* Applies to every later process* call of the engine; NULL restores the Lya-only null model.
+ * GPDLA_EINVAL for L outside 1..31, a non-finite or negative mean_flux_tau_0, a non-finite
+ * mean_flux_beta. */
+int gpdla_engine_set_forest(gpdla_engine* engine, const gpdla_forest* forest);
+/* sum_i t_i(tau_0, beta) at n observed wavelengths (host buffers), by the device function the engine's
+ * forest kernel calls. */
+int gpdla_forest_f64(int32_t device, const double* wavelengths, int64_t n, double z_qso, double tau_0,
+                     double beta, int32_t num_forest_lines, double* out);
+
+/* Sub-DLA model: one absorber at z_j = min_z + (max_z - min_z) offset_j (the engine's own offsets) with
+ * column density nhi_samples[j]; its sample likelihood is the level-1 likelihood with that column
+ * density, its evidence gpdla_engine_process's log-mean-exp (any NaN -> NaN).  It never enters a
+ * multi-DLA chain.  Fused fp64 path only (GPDLA_EUNSUPPORTED otherwise). */
+typedef struct gpdla_sub_dla {
+  const double* nhi_samples;         /* host [S], cm^-2, finite and > 0, in the caller's sample order */
+} gpdla_sub_dla;
+typedef struct gpdla_results_sub {
+  int32_t memory;                      /* GPDLA_MEM_HOST or GPDLA_MEM_DEVICE */
+  double* log_likelihoods_lls;         /* [Q] evidence */
+  double* sample_log_likelihoods_lls;  /* [Q x sample_ld] spectrum-major, or NULL */
+  int64_t sample_ld;                   /* >= S */
+  /* the MAP sample (filled when the call has a summary spec; each may be NULL) */
+  const double* log_nhi_samples;       /* host [S] log10 of nhi_samples; required for the MAP outputs */
+  int32_t* map_sample_inds;            /* [Q] 0-based, -1 = none */
+  double* map_log_likelihoods;         /* [Q] */
+  double* map_z_lls;                   /* [Q] */
+  double* map_log_nhi_lls;             /* [Q] */
+} gpdla_results_sub;
+/* gpdla_engine_process_summaries (spec != NULL) or gpdla_engine_process_multi (spec == NULL) with the
+ * sub-DLA sweep run per device batch after its level 1, while the slot panel is resident.  With
+ * sub == NULL it is that call, bit for bit; with sub, every other result is unchanged bit for bit.
+ * GPDLA_EINVAL for a null, non-positive or non-finite column density or a null results_sub / evidence
+ * array. */
+int gpdla_engine_process_models(gpdla_engine* engine, const gpdla_spectra* spectra,
+                                const gpdla_multi_dla* multi, const gpdla_sub_dla* sub,
+                                const gpdla_results_multi* results_multi, const gpdla_results_sub* results_sub,
+                                const gpdla_summary_spec* spec, const gpdla_summaries* summaries);
+/* Cumulative kernel times (HIP events) and launch counts since create / reset_stats: the forest kernel
+ * and the sub-DLA sweeps (likelihood launch; its log-mean-exp and MAP launches are counted apart). */
+typedef struct gpdla_model_stats {
+  double forest_ms, sub_dla_ms, sub_dla_reduce_ms;
+  int64_t forest_launches, sub_dla_launches, sub_dla_reduce_launches;
+} gpdla_model_stats;
+int gpdla_engine_get_model_stats(gpdla_engine* engine, gpdla_model_stats* stats);
+
 /* voigt MEX replacement (voigt.c:253-304).  Host buffers.  out has n_padded - 6 values. */
 int gpdla_voigt_f64(const double* lambdas, int64_t n_padded, double z, double N,
                     int32_t num_lines, double* out);
