@@ -130,6 +130,23 @@ class ModelStats(C.Structure):
                 ("sub_dla_reduce_launches", C.c_int64)]
 
 
+POPULATION_MAX_LARGE = 8
+PMF_CHUNK = 512
+PMF_MAX_TRIALS = 1 << 18
+
+
+class PopulationSpec(C.Structure):
+    _fields_ = [("log_nhi_samples", dp), ("num_z_bins", C.c_int32), ("num_nhi_bins", C.c_int32),
+                ("z_edges", dp), ("log_nhi_edges", dp), ("p_thresh_sample", C.c_double), ("p_switch", C.c_double),
+                ("p_thresh_spec", C.c_double), ("log_priors_no_dla", dp), ("log_priors_dla", dp),
+                ("log_priors_lls", dp)]
+
+
+class Population(C.Structure):
+    _fields_ = [("memory", C.c_int32), ("poisson_plane", dp), ("large_inds", i32p), ("large_probs", dp),
+                ("large_bins", i32p), ("p_dlas", dp)]
+
+
 class DlaPrior(C.Structure):
     _fields_ = [("alpha", C.c_double), ("uniform_min", C.c_double), ("uniform_max", C.c_double),
                 ("fit_min", C.c_double), ("fit_max", C.c_double), ("fit_upper", C.c_double)]
@@ -169,6 +186,13 @@ SIGNATURES = {
                                               C.POINTER(ResultsMulti), C.POINTER(ResultsSub), C.POINTER(SummarySpec),
                                               C.POINTER(Summaries)]),
     "gpdla_engine_get_model_stats": (C.c_int, [C.c_void_p, C.POINTER(ModelStats)]),
+    "gpdla_engine_process_population": (C.c_int, [C.c_void_p, C.POINTER(Spectra), C.POINTER(MultiDla), C.POINTER(SubDla),
+                                                  C.POINTER(ResultsMulti), C.POINTER(ResultsSub), C.POINTER(SummarySpec),
+                                                  C.POINTER(Summaries), C.POINTER(PopulationSpec), C.POINTER(Population)]),
+    "gpdla_engine_get_population_stats": (C.c_int, [C.c_void_p, dp, i64p]),
+    "gpdla_population_split_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, dp,
+                                             C.POINTER(PopulationSpec), dp, i32p, dp, i32p]),
+    "gpdla_poisson_binomial_pmf_f64": (C.c_int, [C.c_int32, dp, i64p, C.c_int64, dp]),
     "gpdla_resample_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, i32p]),
     "gpdla_voigt_f64": (C.c_int, [dp, C.c_int64, C.c_double, C.c_double, C.c_int32, dp]),
     "gpdla_voigt_batch_f64": (C.c_int, [dp, C.c_int64, dp, dp, C.c_int64, C.c_int32, dp]),

@@ -1,7 +1,8 @@
 """The last stage after ``process_qsos``: the ASCII DLA catalogue (generate_ascii_catalog.m) and the
 binned population moments (CDDF_analysis/calc_cddf.py ``_get_z_nhi_hist``), both from the posterior
 summaries the engine reduces on the device (``Engine.process_summaries``, ``process_qsos(summaries=...)``)
-instead of the Q x S sample array."""
+instead of the Q x S sample array, and the population curves with their confidence bands -- f(N), dN/dX,
+Omega_DLA (calc_cddf.py) -- from the population variables (``process_qsos(population=...)``)."""
 from __future__ import annotations
 
 import os
@@ -46,6 +47,193 @@ def cddf_moments(bin_planes, p_dlas, keep=None, p_thresh_spec: float = 0.05, mom
         variances += p[q] * planes[q, b] - p[q] * p[q] * planes[q, c]
     variances += means
     return means, variances
+
+
+def poisson_binomial_pmf(probs_per_bin, device: int = 0) -> list:
+    """The Poisson-binomial pmf of each trial list, on the device (gpdla_poisson_binomial_pmf_f64): for a list
+    of n probabilities the n + 1 coefficients of prod_j (1 - p_j + p_j x), i.e. Pr(k successes).  It stands
+    where the reference calls ``get_poisson_binomial_pdf`` (calc_cddf.py:1021-1044), but as a product of
+    polynomials with non-negative coefficients instead of a characteristic-function DFT, so the tails keep a
+    relative accuracy.  An empty list gives ``[1.0]`` (:1024-1025).  Returns one array per list."""
+    from .engine import poisson_binomial_pmf_csr
+    lists = [np.ascontiguousarray(p, dtype=np.float64).ravel() for p in probs_per_bin]
+    offsets = np.zeros(len(lists) + 1, dtype=np.int64)
+    np.cumsum([p.size for p in lists], out=offsets[1:])
+    flat = poisson_binomial_pmf_csr(np.concatenate(lists) if lists else np.zeros(0), offsets, device=device)
+    return [flat[offsets[b] + b: offsets[b + 1] + b + 1].copy() for b in range(len(lists))]
+
+
+def _population(out):
+    """The population variables of ``process_qsos(population=...)`` in working form: (Q x nz x nn Poisson
+    plane, Q x 8 0-based sample indices with -1 = none, probabilities, 0-based flat bins, nz, nn)."""
+    plane = np.asarray(out["population_poisson"], dtype=np.float64)
+    if plane.ndim != 3:
+        raise ValueError("population_poisson must be Q x nz x nn")
+    Q, nz, nn = plane.shape
+    inds = np.asarray(out["population_large_inds"], dtype=np.float64).reshape(Q, -1).astype(np.int64) - 1
+    bins = np.asarray(out["population_large_bins"], dtype=np.float64).reshape(Q, -1).astype(np.int64) - 1
+    probs = np.asarray(out["population_large_probs"], dtype=np.float64).reshape(Q, -1)
+    return plane, inds, probs, bins, nz, nn
+
+
+def split_distributions(out, keep=None, p_thresh_spec: float = 0.05, axis: str = "log_nhi"):
+    """``_split_distributions_single`` (calc_cddf.py:724-778) from the population variables the engine reduced
+    (``process_qsos(population=...)``): per bin of ``axis`` -- ``"log_nhi"`` for the CDDF (the grid collapsed
+    over z, ``nhi=True``) or ``"z"`` for dN/dX (collapsed over log N_HI) -- the probabilities kept exactly
+    (p >= p_switch; spectrum by spectrum and in sample order within one, the order the reference appends
+    them in, :771-773) and the mean of the Poisson approximation to the rest (:767-769,774; summed with
+    ``math.fsum`` as there).  Spectra with ``p_dla <= p_thresh_spec`` (:732, ``filter_dla_spectra``) or
+    ``keep`` false contribute nothing.  Returns (list of probability arrays, array of Poisson means)."""
+    import math
+    plane, inds, probs, bins, nz, nn = _population(out)
+    if axis not in ("log_nhi", "z"):
+        raise ValueError("axis must be 'log_nhi' or 'z'")
+    p = np.asarray(out["p_dlas"], dtype=np.float64).ravel()
+    if p.size != plane.shape[0]:
+        raise ValueError("one p_dla per spectrum")
+    use = p > p_thresh_spec
+    if keep is not None:
+        use &= np.asarray(keep, dtype=bool).ravel()
+    nb = nn if axis == "log_nhi" else nz
+    lists = [[] for _ in range(nb)]
+    small = [[] for _ in range(nb)]
+    for q in np.flatnonzero(use):
+        for slot in np.flatnonzero(inds[q] >= 0):          # increasing sample index
+            b = bins[q, slot] % nn if axis == "log_nhi" else bins[q, slot] // nn
+            lists[b].append(probs[q, slot])
+        for b in range(nb):
+            part = plane[q, :, b] if axis == "log_nhi" else plane[q, b, :]
+            small[b].extend(part[part > 0].tolist())
+    return [np.array(v, dtype=np.float64) for v in lists], np.array([math.fsum(v) for v in small])
+
+
+def _interval(cdf, level: float, offset: int = 0):
+    """``interval`` (calc_cddf.py:986-1005; the branch it always takes): the first index at or above the
+    lower tail and one past the first index above the upper one; a cdf that never exceeds the upper level
+    gives its length, without the offset, as there (:1003)."""
+    cdf = np.asarray(cdf)
+    if cdf.size == 1:
+        return offset, offset
+    low, high = offset, 1 + offset
+    down = np.flatnonzero(cdf < 0.5 - level / 2)
+    if down.size:
+        low += int(down[-1]) + 1
+    up = np.flatnonzero(cdf > 0.5 + level / 2)
+    high = high + int(up[0]) if up.size else int(cdf.size)
+    return low, high
+
+
+def count_intervals(pmf, poisson_mean: float):
+    """``_get_combined_levels`` and ``pdf_confidence`` (calc_cddf.py:780-798, 1007-1019): the pmf of the
+    exactly kept trials convolved with the Poisson pmf of mean ``poisson_mean``, both cut to their central
+    1 - 1e-4 (:789-796; a zero mean leaves the pmf alone, :784-785), then the count at which the cdf reaches
+    one half and the 68 % and 95 % intervals.  Returns (count, (low68, high68), (low95, high95)), integers."""
+    import math
+    pmf = np.asarray(pmf, dtype=np.float64).ravel()
+    offset = 0
+    if poisson_mean != 0.0:
+        from scipy.stats import poisson
+        weak = poisson(poisson_mean)
+        plow, phigh = (int(v) for v in weak.interval(1 - 1e-4))
+        dlow, dhigh = _interval(np.cumsum(pmf), 1 - 1e-4)
+        top = min(dhigh + 1, pmf.size)
+        pmf = np.array([math.fsum(weak.pmf(n - i) * pmf[i] for i in range(dlow, top))
+                        for n in range(plow + dlow, phigh + dhigh + 1)])
+        offset = plow + dlow
+    cdf = np.cumsum(pmf)
+    return _interval(cdf, 0.0, offset)[0], _interval(cdf, 0.68, offset), _interval(cdf, 0.95, offset)
+
+
+def confidence_intervals(out, keep=None, p_thresh_spec: float = 0.05, axis: str = "log_nhi", device: int = 0, pmf=None):
+    """``_get_confidence_intervals`` (calc_cddf.py:800-827): ``split_distributions``, the device pmf of every
+    bin's exact list and ``count_intervals``.  ``pmf(lists)`` replaces the device call (tests, as ``compute``
+    does for ``process_qsos``).  Returns (counts [nb], intervals68 [nb x 2], intervals95 [nb x 2])."""
+    lists, means = split_distributions(out, keep, p_thresh_spec, axis)
+    pmfs = poisson_binomial_pmf(lists, device=device) if pmf is None else pmf(lists)
+    got = [count_intervals(one, mean) for one, mean in zip(pmfs, means)]
+    return (np.array([g[0] for g in got]), np.array([g[1] for g in got]).reshape(-1, 2),
+            np.array([g[2] for g in got]).reshape(-1, 2))
+
+
+def absorption_distance(z, omega_m: float = 0.279):
+    """X(z) with dX = (1 + z)^2 H_0 / H(z) dz (calc_cddf.py:1058-1063, flat LCDM without radiation, :978-984):
+    the integrand has the antiderivative 2 sqrt(Omega_m (1 + z)^3 + 1 - Omega_m) / (3 Omega_m)."""
+    z = np.asarray(z, dtype=np.float64)
+    return 2.0 * np.sqrt(omega_m * (1.0 + z) ** 3 + (1.0 - omega_m)) / (3.0 * omega_m)
+
+
+def path_length(z_lo: float, z_hi: float, min_z_dlas, max_z_dlas, keep=None, omega_m: float = 0.279) -> float:
+    """The absorption path searched between ``z_lo`` and ``z_hi`` (calc_cddf.py:334-385 without pixel
+    filtering): every spectrum with ``keep`` true (the reference's SNR / condition mask, :347; no p_dla cut)
+    whose search range overlaps the interval (:355) contributes X(min(z_hi, max_z)) - X(max(z_lo, min_z)).
+    Vectorised over spectra.  No quadrature: the antiderivative is closed (``absorption_distance``), so a
+    spectrum's term is exact to a few ulp of X (< 4e-15 absolute below z = 7), where the reference's ``quad``
+    stops at 1.5e-8 per integral."""
+    import math
+    if not z_lo < z_hi:
+        raise ValueError("z_lo must be below z_hi")
+    zmin = np.asarray(min_z_dlas, dtype=np.float64).ravel()
+    zmax = np.asarray(max_z_dlas, dtype=np.float64).ravel()
+    use = (zmin < z_hi) & (zmax > z_lo)
+    if keep is not None:
+        use &= np.asarray(keep, dtype=bool).ravel()
+    hi, lo = np.minimum(z_hi, zmax[use]), np.maximum(z_lo, zmin[use])
+    return math.fsum(absorption_distance(hi, omega_m) - absorption_distance(lo, omega_m))
+
+
+def column_density_function(out, keep=None, p_thresh_spec: float = 0.05, omega_m: float = 0.279, device: int = 0,
+                            pmf=None):
+    """f(N) = n_DLA / dN / dX (calc_cddf.py:440-464) on the population grid of ``out``: the log N_HI bins are
+    ``population_log_nhi_edges`` and the redshift range its whole z extent.  Returns (bin centres in log N_HI,
+    f(N), its 68 % band [nn x 2], its 95 % band, (lower, upper) bin half-widths in N_HI)."""
+    ez = np.asarray(out["population_z_edges"], dtype=np.float64).ravel()
+    en = np.asarray(out["population_log_nhi_edges"], dtype=np.float64).ravel()
+    n, l68, l95 = confidence_intervals(out, keep, p_thresh_spec, "log_nhi", device, pmf)
+    dX = path_length(ez[0], ez[-1], out["min_z_dlas"], out["max_z_dlas"], keep, omega_m)
+    dN = 10.0 ** en[1:] - 10.0 ** en[:-1]
+    cent = (en[1:] + en[:-1]) / 2.0
+    xerrs = (10.0 ** cent - 10.0 ** en[:-1], 10.0 ** en[1:] - 10.0 ** cent)
+    return cent, n / dX / dN, l68 / dX / dN[:, None], l95 / dX / dN[:, None], xerrs
+
+
+def line_density(out, keep=None, p_thresh_spec: float = 0.05, omega_m: float = 0.279, device: int = 0, pmf=None):
+    """dN/dX per redshift bin (calc_cddf.py:490-507) on the population grid of ``out``: the bins are
+    ``population_z_edges`` and the column densities its whole log N_HI extent; bins without path are dropped
+    (:500).  Returns (bin centres, dN/dX, 68 % band, 95 % band, (lower, upper) half-widths)."""
+    ez = np.asarray(out["population_z_edges"], dtype=np.float64).ravel()
+    n, l68, l95 = confidence_intervals(out, keep, p_thresh_spec, "z", device, pmf)
+    dX = np.array([path_length(a, b, out["min_z_dlas"], out["max_z_dlas"], keep, omega_m) for a, b in zip(ez[:-1], ez[1:])])
+    ii = dX > 0
+    cent = (ez[1:] + ez[:-1]) / 2.0
+    xerrs = (cent[ii] - ez[:-1][ii], ez[1:][ii] - cent[ii])
+    return cent[ii], n[ii] / dX[ii], l68[ii] / dX[ii, None], l95[ii] / dX[ii, None], xerrs
+
+
+PROTON_MASS_G = 1.67262178e-24        # calc_cddf.py:651
+H100_PER_S = 3.2407789e-18            # 100 km/s/Mpc in 1/s (:655)
+LIGHT_CM_PER_S = 2.99e10              # :657, the reference's own rounding
+GRAVITY_CGS = 6.674e-8                # :1070
+
+
+def rho_crit(hubble: float = 0.7) -> float:
+    """Critical density at z = 0 in g cm^-3 (calc_cddf.py:1065-1072)."""
+    import math
+    return 3.0 * (H100_PER_S * hubble) ** 2 / (8.0 * math.pi * GRAVITY_CGS)
+
+
+def omega_dla(out, keep=None, p_thresh_spec: float = 0.05, hubble: float = 0.7, omega_m: float = 0.279):
+    """Omega_DLA per redshift bin by summing column densities (calc_cddf.py:638-662), the moment version:
+    ``cddf_moments(moment=True)`` on the summary grid of ``out`` (``bin_planes`` with ``bin_z_edges``; every
+    log N_HI bin of it counts) over the path lengths, in the reference's units -- m_p H_0 / (c rho_crit), with
+    rho_crit at the reference's default h = 0.7 whatever ``hubble`` is (:658 calls it without the argument).
+    Returns (bin centres, Omega_DLA, its standard deviation, the z edges)."""
+    ez = np.asarray(out["bin_z_edges"], dtype=np.float64).ravel()
+    means, variances = cddf_moments(out["bin_planes"], out["p_dlas"], keep, p_thresh_spec, moment=True)
+    mean, variance = means.sum(axis=1), variances.sum(axis=1)
+    dX = np.array([path_length(a, b, out["min_z_dlas"], out["max_z_dlas"], keep, omega_m) for a, b in zip(ez[:-1], ez[1:])])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        conversion = PROTON_MASS_G * (H100_PER_S * hubble) / LIGHT_CM_PER_S / dX / rho_crit()
+    return (ez[1:] + ez[:-1]) / 2.0, mean * conversion, np.sqrt(variance) * conversion, ez
 
 
 def _fmt(spec: str, value) -> str:

@@ -99,7 +99,8 @@ struct TimedLaunch {
   int kind;  // 0 prep, 1 likelihood, 2 reduce, 3 contraction (panel-GEMM paths, inside 1);
              // gpdla_engine_process_multi only: 4 resample, 5 level >= 2 sweep, 6 its log-mean-exp;
              // 7 posterior summaries (gpdla_engine_process_summaries); 8 forest kernel; gpdla_engine_process_models
-             // only: 9 sub-DLA sweep, 10 its log-mean-exp and MAP launches
+             // only: 9 sub-DLA sweep, 10 its log-mean-exp and MAP launches; 11 population launches
+             // (gpdla_engine_process_population)
   int level; // multi-DLA level the span also counts for in gpdla_multi_stats (0: none)
 };
 
@@ -222,6 +223,17 @@ struct gpdla_engine {
          cap_sub_mll = 0, cap_sub_mz = 0, cap_sub_mn = 0, cap_sub_mind = 0;
   gpdla_model_stats model_stats{};
 
+  // population statistics (gpdla_engine_process_population): the call's log priors ([Q], [D][Q], [Q]),
+  // its samples' log10 N_HI and grid edges, and a batch's outputs ([nq] p_dla, [nq][bins] Poisson plane,
+  // [nq][8] large samples)
+  double *d_p_lpno = nullptr, *d_p_lpdla = nullptr, *d_p_lplls = nullptr, *d_p_lognhi = nullptr, *d_p_edges = nullptr,
+         *d_p_pdla = nullptr, *d_p_plane = nullptr, *d_p_lprob = nullptr;
+  int32_t *d_p_lind = nullptr, *d_p_lbin = nullptr;
+  size_t cap_p_lpno = 0, cap_p_lpdla = 0, cap_p_lplls = 0, cap_p_lognhi = 0, cap_p_edges = 0, cap_p_pdla = 0,
+         cap_p_plane = 0, cap_p_lprob = 0, cap_p_lind = 0, cap_p_lbin = 0;
+  double population_ms = 0.0;
+  int64_t population_launches = 0;
+
   std::vector<TimedLaunch> pending;
   gpdla_stats stats{};
 };
@@ -251,6 +263,7 @@ int resolve_events(gpdla_engine* e) {
     if (t.kind == 8) { e->model_stats.forest_ms += ms; e->model_stats.forest_launches++; }
     if (t.kind == 9) { e->model_stats.sub_dla_ms += ms; e->model_stats.sub_dla_launches++; }
     if (t.kind == 10) { e->model_stats.sub_dla_reduce_ms += ms; e->model_stats.sub_dla_reduce_launches++; }
+    if (t.kind == 11) { e->population_ms += ms; e->population_launches++; }
     if (t.level >= 1 && t.level <= GPDLA_MAX_DLAS) {
       e->mstats.level_ms[t.level - 1] += ms;
       e->mstats.level_launches[t.level - 1]++;
@@ -356,7 +369,8 @@ void gpdla_engine_destroy(gpdla_engine* e) {
                   e->d_m_chain[0], e->d_m_chain[1], e->d_m_forced, e->d_s_lognhi, e->d_s_edges,
                   e->d_s_ll, e->d_s_z, e->d_s_n, e->d_s_planes, e->d_s_ind, e->d_sub_nhi, e->d_sub_nhi_c,
                   e->d_sub_lognhi, e->d_sub_sll, e->d_sub_ev, e->d_sub_null, e->d_sub_mll, e->d_sub_mz,
-                  e->d_sub_mn, e->d_sub_mind};
+                  e->d_sub_mn, e->d_sub_mind, e->d_p_lpno, e->d_p_lpdla, e->d_p_lplls, e->d_p_lognhi, e->d_p_edges,
+                  e->d_p_pdla, e->d_p_plane, e->d_p_lprob, e->d_p_lind, e->d_p_lbin};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (e->h_meta) (void)hipHostFree(e->h_meta);
@@ -1055,6 +1069,8 @@ int gpdla_engine_reset_stats(gpdla_engine* e) {
   e->mstats = gpdla_multi_stats{};
   e->summary_ms = 0.0;
   e->summary_launches = 0;
+  e->population_ms = 0.0;
+  e->population_launches = 0;
   e->model_stats = gpdla_model_stats{};
   return GPDLA_OK;
 }
@@ -1122,11 +1138,27 @@ static int validate_summary_grid(const gpdla_summary_spec* spec) {
 // runs per batch after the last level, on the level workspaces the batch leaves on the device
 // With sub / rsub (gpdla_engine_process_models) the sub-DLA sweep runs per batch after its level 1: the
 // level-1 likelihood launch again with the sub-DLA column densities, into workspaces of its own.
+// With pspec / pop (gpdla_engine_process_population) the posterior and split launches of population.hip
+// run per batch after the last level, on the batch's evidences and level-1 rows.
 static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
                               const gpdla_results_multi* res, const gpdla_summary_spec* spec,
                               const gpdla_summaries* sums, const gpdla_sub_dla* sub = nullptr,
-                              const gpdla_results_sub* rsub = nullptr) {
+                              const gpdla_results_sub* rsub = nullptr, const gpdla_population_spec* pspec = nullptr,
+                              const gpdla_population* pop = nullptr) {
   if (!e || !sp || !mu || !res) return set_error(GPDLA_EINVAL, "null argument");
+  if (pspec) {
+    if (!pop) return set_error(GPDLA_EINVAL, "null argument");
+    int rcp = validate_population_grid(pspec->num_z_bins, pspec->num_nhi_bins, pspec->z_edges, pspec->log_nhi_edges,
+                                       pspec->p_thresh_sample, pspec->p_switch);
+    if (rcp) return rcp;
+    if (!pspec->log_nhi_samples) return set_error(GPDLA_EINVAL, "null population log_nhi_samples");
+    if (!pspec->log_priors_no_dla || !pspec->log_priors_dla || (sub && !pspec->log_priors_lls))
+      return set_error(GPDLA_EINVAL, "null population prior array");
+    if (!pop->poisson_plane || !pop->large_inds || !pop->large_probs || !pop->large_bins || !pop->p_dlas)
+      return set_error(GPDLA_EINVAL, "null population array");
+    if (pop->memory != GPDLA_MEM_HOST && pop->memory != GPDLA_MEM_DEVICE)
+      return set_error(GPDLA_EINVAL, "population memory=%d", pop->memory);
+  }
   bool sub_map = false;
   if (sub) {
     if (!rsub || !rsub->log_likelihoods_lls) return set_error(GPDLA_EINVAL, "null sub-DLA result array");
@@ -1184,7 +1216,7 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
     return set_error(GPDLA_EINVAL, "sample_ld (%lld) < num_samples (%lld)", (long long)res->sample_ld, (long long)S);
   HIP_TRY(hipSetDevice(e->device));
   int rc;
-  if ((D > 1 || spec) && (rc = multi_caller_samples(e))) return rc;
+  if ((D > 1 || spec || pspec) && (rc = multi_caller_samples(e))) return rc;
   hipStream_t st = e->stream;
   if (sub) {  // the column densities in the sweep's (ascending-offset) order, as the engine's own are kept
     const size_t Ss = (size_t)S;
@@ -1210,6 +1242,24 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
       if ((rc = grow(&e->d_s_edges, &e->cap_s_edges, (size_t)(nzb + nnb + 2)))) return rc;
       HIP_TRY(hipMemcpyAsync(e->d_s_edges, spec->z_edges, (size_t)(nzb + 1) * 8, hipMemcpyHostToDevice, st));
       HIP_TRY(hipMemcpyAsync(e->d_s_edges + nzb + 1, spec->log_nhi_edges, (size_t)(nnb + 1) * 8, hipMemcpyHostToDevice, st));
+    }
+  }
+  const int pnz = pspec ? pspec->num_z_bins : 0, pnn = pspec ? pspec->num_nhi_bins : 0;
+  const size_t pbins = (size_t)pnz * pnn;
+  if (pspec) {
+    const size_t Qs = (size_t)Q;
+    if ((rc = grow(&e->d_p_lognhi, &e->cap_p_lognhi, (size_t)S))) return rc;
+    if ((rc = grow(&e->d_p_edges, &e->cap_p_edges, (size_t)(pnz + pnn + 2)))) return rc;
+    if ((rc = grow(&e->d_p_lpno, &e->cap_p_lpno, Qs))) return rc;
+    if ((rc = grow(&e->d_p_lpdla, &e->cap_p_lpdla, Qs * D))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_p_lognhi, pspec->log_nhi_samples, (size_t)S * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_p_edges, pspec->z_edges, (size_t)(pnz + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_p_edges + pnz + 1, pspec->log_nhi_edges, (size_t)(pnn + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_p_lpno, pspec->log_priors_no_dla, Qs * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_p_lpdla, pspec->log_priors_dla, Qs * D * 8, hipMemcpyHostToDevice, st));
+    if (sub) {
+      if ((rc = grow(&e->d_p_lplls, &e->cap_p_lplls, Qs))) return rc;
+      HIP_TRY(hipMemcpyAsync(e->d_p_lplls, pspec->log_priors_lls, Qs * 8, hipMemcpyHostToDevice, st));
     }
   }
   const bool out_dev = res->memory == GPDLA_MEM_DEVICE;
@@ -1385,6 +1435,38 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
                                (size_t)nq * kSummaryPlanes * nbins * 8, sk, st));
     }
 
+    if (pspec) {
+      const size_t NL = kPopulationMaxLarge;
+      if ((rc = grow(&e->d_p_pdla, &e->cap_p_pdla, (size_t)nq))) return rc;
+      if ((rc = grow(&e->d_p_plane, &e->cap_p_plane, (size_t)nq * pbins))) return rc;
+      if ((rc = grow(&e->d_p_lind, &e->cap_p_lind, (size_t)nq * NL))) return rc;
+      if ((rc = grow(&e->d_p_lprob, &e->cap_p_lprob, (size_t)nq * NL))) return rc;
+      if ((rc = grow(&e->d_p_lbin, &e->cap_p_lbin, (size_t)nq * NL))) return rc;
+      ModelPosteriorArgs ma{};
+      ma.rows = (int32_t)nq; ma.levels = D; ma.ll_null = e->d_m_null; ma.ll_dla = e->d_m_lldla;
+      ma.ll_lls = sub ? e->d_sub_ev : nullptr;
+      ma.lp_no = e->d_p_lpno + q0; ma.lp_dla = e->d_p_lpdla + q0; ma.lp_lls = sub ? e->d_p_lplls + q0 : nullptr;
+      ma.ld_prior = Q; ma.p_dla = e->d_p_pdla;
+      PopulationSplitArgs pa{};
+      pa.rows = (int32_t)nq; pa.ll = e->d_m_sll; pa.ld = S; pa.S = S;
+      pa.offset = e->d_off_c; pa.log_nhi = e->d_p_lognhi; pa.zmin = e->d_m_zmin; pa.zmax = e->d_m_zmax;
+      pa.p_dla = e->d_p_pdla; pa.nz = pnz; pa.nn = pnn; pa.z_edges = e->d_p_edges; pa.n_edges = e->d_p_edges + pnz + 1;
+      pa.p_thresh_sample = pspec->p_thresh_sample; pa.p_switch = pspec->p_switch;
+      pa.poisson = e->d_p_plane; pa.large_inds = e->d_p_lind; pa.large_probs = e->d_p_lprob; pa.large_bins = e->d_p_lbin;
+      TimedLaunch t11{};
+      if ((rc = record_start(e, &t11, 11))) return rc;
+      HIP_TRY(launch_model_posterior(ma, st));
+      HIP_TRY(launch_population_split(pa, st));
+      HIP_TRY(hipEventRecord(t11.stop, st));
+      e->pending.push_back(t11);
+      const hipMemcpyKind pk = pop->memory == GPDLA_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+      HIP_TRY(hipMemcpyAsync(pop->p_dlas + q0, e->d_p_pdla, nq * 8, pk, st));
+      HIP_TRY(hipMemcpyAsync(pop->poisson_plane + (size_t)q0 * pbins, e->d_p_plane, (size_t)nq * pbins * 8, pk, st));
+      HIP_TRY(hipMemcpyAsync(pop->large_inds + (size_t)q0 * NL, e->d_p_lind, (size_t)nq * NL * 4, pk, st));
+      HIP_TRY(hipMemcpyAsync(pop->large_probs + (size_t)q0 * NL, e->d_p_lprob, (size_t)nq * NL * 8, pk, st));
+      HIP_TRY(hipMemcpyAsync(pop->large_bins + (size_t)q0 * NL, e->d_p_lbin, (size_t)nq * NL * 4, pk, st));
+    }
+
     HIP_TRY(hipMemcpyAsync(res->log_likelihoods_no_dla + q0, e->d_m_null, nq * 8, out_kind, st));
     if (res->min_z_dlas) HIP_TRY(hipMemcpyAsync(res->min_z_dlas + q0, e->d_m_zmin, nq * 8, out_kind, st));
     if (res->max_z_dlas) HIP_TRY(hipMemcpyAsync(res->max_z_dlas + q0, e->d_m_zmax, nq * 8, out_kind, st));
@@ -1427,6 +1509,28 @@ int gpdla_engine_process_models(gpdla_engine* e, const gpdla_spectra* sp, const 
   if (spec && !sums) return set_error(GPDLA_EINVAL, "null argument");
   if (sub && !rsub) return set_error(GPDLA_EINVAL, "null sub-DLA results");
   return process_multi_impl(e, sp, mu, res, spec, spec ? sums : nullptr, sub, sub ? rsub : nullptr);
+}
+
+int gpdla_engine_process_population(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
+                                    const gpdla_sub_dla* sub, const gpdla_results_multi* res,
+                                    const gpdla_results_sub* rsub, const gpdla_summary_spec* spec,
+                                    const gpdla_summaries* sums, const gpdla_population_spec* pspec,
+                                    const gpdla_population* pop) {
+  if (spec && !sums) return set_error(GPDLA_EINVAL, "null argument");
+  if (sub && !rsub) return set_error(GPDLA_EINVAL, "null sub-DLA results");
+  if ((pspec == nullptr) != (pop == nullptr)) return set_error(GPDLA_EINVAL, "population spec and outputs go together");
+  return process_multi_impl(e, sp, mu, res, spec, spec ? sums : nullptr, sub, sub ? rsub : nullptr, pspec, pop);
+}
+
+int gpdla_engine_get_population_stats(gpdla_engine* e, double* ms, int64_t* launches) {
+  if (!e || !ms || !launches) return set_error(GPDLA_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  int rc = resolve_events(e);
+  if (rc) return rc;
+  *ms = e->population_ms;
+  *launches = e->population_launches;
+  return GPDLA_OK;
 }
 
 int gpdla_engine_set_forest(gpdla_engine* e, const gpdla_forest* f) {

@@ -535,6 +535,58 @@ struct SummaryArgs {
 };
 hipError_t launch_posterior_summary(const SummaryArgs& a, hipStream_t s);
 
+// ---- population statistics (population.hip): the model posteriors' p_dla per spectrum, the split of
+// the level-1 masses p_dla pi_j into a Poisson plane and a short list of large probabilities, and the
+// Poisson-binomial pmf of CSR trial lists
+constexpr int kPopulationMaxLarge = 8;
+constexpr int kPmfChunk = 512;           // trials per chunk polynomial
+struct ModelPosteriorArgs {
+  int32_t rows, levels;
+  const double* ll_null;         // [rows]
+  const double* ll_dla;          // [levels][rows]
+  const double* ll_lls;          // [rows], or nullptr: no sub-DLA model
+  const double* lp_no;           // [rows] log priors
+  const double* lp_dla;          // [levels][ld_prior]
+  const double* lp_lls;          // [rows] with ll_lls
+  int64_t ld_prior;
+  double* p_dla;                 // [rows]
+};
+struct PopulationSplitArgs {
+  int32_t rows;
+  const double* ll;              // [rows][ld], level 1, caller's sample order
+  int64_t ld, S;
+  const double* offset;          // [S]
+  const double* log_nhi;         // [S]
+  const double *zmin, *zmax;     // [rows]
+  const double* p_dla;           // [rows]
+  int32_t nz, nn;
+  const double* z_edges;         // device [nz + 1]
+  const double* n_edges;         // device [nn + 1]
+  double p_thresh_sample, p_switch;
+  double* poisson;               // [rows][nz nn]
+  int32_t* large_inds;           // [rows][kPopulationMaxLarge], -1 = unused
+  double* large_probs;           // NaN = unused
+  int32_t* large_bins;           // iz nn + in, -1 = unused
+};
+struct PmfChunkArgs {
+  const double* probs;
+  const int64_t* start;          // [chunks] first trial
+  const int32_t* len;            // [chunks] 0..kPmfChunk trials
+  double* const* dst;            // [chunks] where the len + 1 coefficients go
+};
+struct PmfFoldArgs {             // the bins of more than one chunk
+  const int64_t* n;              // trials
+  const int64_t* out_off;        // the bin's offset in either fold buffer (and in the output)
+  const int64_t* chunk_off;      // the bin's offset in the chunk store
+  const int32_t* nch;            // chunks
+  const double* chunks;
+  double* buf[2];
+};
+hipError_t launch_model_posterior(const ModelPosteriorArgs& a, hipStream_t s);
+hipError_t launch_population_split(const PopulationSplitArgs& a, hipStream_t s);
+int validate_population_grid(int64_t nz, int64_t nn, const double* z_edges, const double* n_edges,
+                             double p_thresh_sample, double p_switch);
+
 // ---- Lyman-series forest (forest.hip): rewrites the kMu / kOmega2 words of a batch's valid slots
 // between prep_kernel and the sweeps (fused fp64 layout only)
 struct ForestArgs {

@@ -20,6 +20,7 @@
 
 #include "../../include/gpdla.h"
 #include "internal.h"
+#include "sample_bins.h"
 
 namespace gpdla {
 namespace {
@@ -51,26 +52,6 @@ __host__ __device__ inline SummaryLds summary_lds(int nz, int nn, bool planes) {
   }
   l.total = o;
   return l;
-}
-
-// z_j = min_z + (max_z - min_z) * offset_j with each operation rounded on its own, as numpy (and
-// process_qsos.m:163) forms it: a fused multiply-add would move samples across bin edges
-__device__ __forceinline__ double sample_z(double zmin, double zmax, double off) {
-#pragma clang fp contract(off)
-  const double span = zmax - zmin;
-  const double t = span * off;
-  return zmin + t;
-}
-
-// the i with e[i] <= x < e[i + 1], or -1 (also for NaN); e[0..n] strictly increasing
-__device__ __forceinline__ int find_bin(const double* e, int n, double x) {
-  if (!(x >= e[0]) || !(x < e[n])) return -1;
-  int lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (x >= e[mid]) lo = mid; else hi = mid;
-  }
-  return lo;
 }
 
 __global__ __launch_bounds__(kSummaryThreads) void posterior_summary_kernel(SummaryArgs a) {

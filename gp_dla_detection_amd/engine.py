@@ -190,10 +190,12 @@ class Engine:
         return dict(summary_ms=ms.value, summary_launches=n.value)
 
     def _run_multi(self, packed, max_dlas, resample_uniforms, base_sample_inds, want_samples, min_z_separation,
-                   occam_log_penalty, raise_numeric, memory, summary, sub=None, models=False) -> dict:
-        """process_multi / process_summaries / process_models: ``summary`` is None or the samples' log N_HI
-        and the grid; ``sub`` None or the sub-DLA column densities (``nhi``) and, for the MAP outputs, their
-        log10 (``log_nhi``); ``models`` routes the call through gpdla_engine_process_models."""
+                   occam_log_penalty, raise_numeric, memory, summary, sub=None, models=False, population=None) -> dict:
+        """process_multi / process_summaries / process_models / process_population: ``summary`` is None or
+        the samples' log N_HI and the grid; ``sub`` None or the sub-DLA column densities (``nhi``) and, for the
+        MAP outputs, their log10 (``log_nhi``); ``models`` routes the call through gpdla_engine_process_models,
+        ``models="population"`` through gpdla_engine_process_population with ``population`` None (both structs
+        NULL) or the normalised dict of ``process_population``."""
         D, S = int(max_dlas), self.num_samples
         offsets = np.ascontiguousarray(packed["offsets"], dtype=np.int64)
         Q = offsets.size - 1
@@ -250,6 +252,33 @@ class Engine:
                 subout.update(map_sample_ind_lls=np.full(Q, -1, dtype=np.int32), map_log_likelihood_lls=np.full(Q, np.nan),
                               MAP_z_lls=np.full(Q, np.nan), MAP_log_nhi_lls=np.full(Q, np.nan))
 
+        pspec, pout = None, {}
+        if population is not None:
+            pz, pn = population["z_edges"], population["log_nhi_edges"]
+            lp_no, lp_dla, lp_lls = population["log_priors_no_dla"], population["log_priors_dla"], population["log_priors_lls"]
+            if lp_no.shape != (Q,) or lp_dla.shape != (Dc, Q) or (lp_lls is not None and lp_lls.shape != (Q,)):
+                raise ValueError(f"population priors must be {(Q,)}, {(Dc, Q)} and {(Q,)}")
+            if sub is not None and lp_lls is None:
+                raise ValueError("population with the sub-DLA model needs log_priors_lls")
+            pspec = L.PopulationSpec(log_nhi_samples=L.ptr(population["log_nhi"]), num_z_bins=pz.size - 1,
+                                     num_nhi_bins=pn.size - 1, z_edges=L.ptr(pz), log_nhi_edges=L.ptr(pn),
+                                     p_thresh_sample=population["p_thresh_sample"], p_switch=population["p_switch"],
+                                     p_thresh_spec=population["p_thresh_spec"], log_priors_no_dla=L.ptr(lp_no),
+                                     log_priors_dla=L.ptr(lp_dla), log_priors_lls=L.ptr(lp_lls))
+            pout = dict(population_poisson=np.zeros((Q, max(pz.size - 1, 0), max(pn.size - 1, 0))),
+                        population_large_inds=np.full((Q, L.POPULATION_MAX_LARGE), -1, dtype=np.int32),
+                        population_large_probs=np.full((Q, L.POPULATION_MAX_LARGE), np.nan),
+                        population_large_bins=np.full((Q, L.POPULATION_MAX_LARGE), -1, dtype=np.int32),
+                        population_p_dlas=np.full(Q, np.nan))
+
+        def results_pop(mem, get):
+            if pspec is None:
+                return None
+            return L.Population(memory=mem, poisson_plane=get("population_poisson"),
+                                large_inds=get("population_large_inds", C.c_int32),
+                                large_probs=get("population_large_probs"),
+                                large_bins=get("population_large_bins", C.c_int32), p_dlas=get("population_p_dlas"))
+
         def results_sub(mem, get):
             if sub is None:
                 return None
@@ -260,7 +289,13 @@ class Engine:
                                 map_log_likelihoods=get("map_log_likelihood_lls"), map_z_lls=get("MAP_z_lls"),
                                 map_log_nhi_lls=get("MAP_log_nhi_lls"))
 
-        def call(sp, rs, sm, rsub=None):
+        def call(sp, rs, sm, rsub=None, rpop=None):
+            if models == "population":
+                return self.lib.gpdla_engine_process_population(
+                    self._h, C.byref(sp), C.byref(md), C.byref(subs) if subs is not None else None, C.byref(rs),
+                    C.byref(rsub) if rsub is not None else None, C.byref(spec) if spec is not None else None,
+                    C.byref(sm) if sm is not None else None, C.byref(pspec) if pspec is not None else None,
+                    C.byref(rpop) if rpop is not None else None)
             if models:
                 return self.lib.gpdla_engine_process_models(
                     self._h, C.byref(sp), C.byref(md), C.byref(subs) if subs is not None else None, C.byref(rs),
@@ -288,7 +323,8 @@ class Engine:
                                  map_log_likelihoods=L.ptr(sout["map_log_likelihoods"]),
                                  map_z_dlas=L.ptr(sout["map_z_dlas"]), map_log_nhis=L.ptr(sout["map_log_nhis"]),
                                  bin_planes=L.ptr(pl) if pl is not None and pl.size else None)
-            rc = call(sp, rs, sm, results_sub(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(subout.get(k), t)))
+            rc = call(sp, rs, sm, results_sub(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(subout.get(k), t)),
+                      results_pop(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(pout[k], t) if pout[k].size else None))
         elif memory == "device":
             dev = {k: L.DeviceArray.from_numpy(v, self.device) for k, v in
                    dict(wl=wl, fl=fl, nv=nv, mk=mk, zq=zq).items()}
@@ -317,15 +353,19 @@ class Engine:
                                  map_log_likelihoods=sptr("map_log_likelihoods"), map_z_dlas=sptr("map_z_dlas"),
                                  map_log_nhis=sptr("map_log_nhis"), bin_planes=sptr("bin_planes"))
             dsub = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in subout.items() if v.size}
-            rc = call(sp, rs, sm, results_sub(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dsub[k].ptr, t) if k in dsub else None))
+            dpop = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in pout.items() if v.size}
+            rc = call(sp, rs, sm, results_sub(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dsub[k].ptr, t) if k in dsub else None),
+                      results_pop(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dpop[k].ptr, t) if k in dpop else None))
             if rc in (L.GPDLA_OK, L.GPDLA_ENUMERIC):
+                for k, d in dpop.items():
+                    pout[k] = d.numpy()
                 for k, d in dout.items():
                     out[k] = d.numpy()
                 for k, d in dsum.items():
                     sout[k] = d.numpy()
                 for k, d in dsub.items():
                     subout[k] = d.numpy()
-            for d in list(dev.values()) + list(dout.values()) + list(dsum.values()) + list(dsub.values()):
+            for d in list(dev.values()) + list(dout.values()) + list(dsum.values()) + list(dsub.values()) + list(dpop.values()):
                 d.free()
         else:
             raise ValueError("memory must be 'host' or 'device'")
@@ -340,6 +380,7 @@ class Engine:
             if "bin_planes" in sout:
                 out["bin_planes"] = sout["bin_planes"]
         out.update(subout)
+        out.update(pout)
         return out
 
     # --------------------------------------------------------------------- sub-DLA model and forest
@@ -375,6 +416,13 @@ class Engine:
         ``map_log_likelihood_lls``, ``MAP_z_lls`` and ``MAP_log_nhi_lls`` (Q; ``sub_dla_log_nhi`` defaults to
         log10 of ``sub_dla``).  Every other array is the plain call's, bit for bit; ``sub_dla=None`` is
         exactly that call."""
+        return self._process_models(packed, max_dlas, sub_dla, log_nhi_samples, z_edges, log_nhi_edges, sub_dla_log_nhi,
+                                    want_samples, True, None, kwargs)
+
+    def _process_models(self, packed, max_dlas, sub_dla, log_nhi_samples, z_edges, log_nhi_edges, sub_dla_log_nhi,
+                        want_samples, entry, population, kwargs) -> dict:
+        """``process_models`` / ``process_population``: ``entry`` and ``population`` are ``_run_multi``'s
+        ``models`` and ``population``."""
         if (z_edges is None) != (log_nhi_edges is None):
             raise ValueError("z_edges and log_nhi_edges go together")
         if z_edges is not None and log_nhi_samples is None:
@@ -405,7 +453,59 @@ class Engine:
             raise TypeError(f"unexpected keyword arguments {sorted(unknown)}")
         return self._run_multi(packed, max_dlas, kwargs.get("resample_uniforms"), kwargs.get("base_sample_inds"),
                                want_samples, kwargs.get("min_z_separation"), kwargs.get("occam_log_penalty"),
-                               kwargs.get("raise_numeric", False), kwargs.get("memory", "host"), summary, sub, True)
+                               kwargs.get("raise_numeric", False), kwargs.get("memory", "host"), summary, sub, entry,
+                               population)
+
+    def process_population(self, packed: dict, max_dlas: int = 1, population=None, sub_dla=None, log_nhi_samples=None,
+                           z_edges=None, log_nhi_edges=None, sub_dla_log_nhi=None, want_samples: bool = True,
+                           **kwargs) -> dict:
+        """``process_models`` (its arguments pass through) plus the population statistics reduced on the device
+        (gpdla_engine_process_population).  ``population`` is a dict of ``z_edges``,
+        ``log_nhi_edges`` (a grid of its own, independent of a summary grid), ``log_nhi_samples`` (the engine's
+        samples' log10 N_HI), ``log_priors_no_dla`` (Q), ``log_priors_dla`` (D x Q, or Q for D = 1),
+        ``log_priors_lls`` (Q, with ``sub_dla``) and optionally ``p_thresh_sample`` (1e-4), ``p_switch`` (0.25),
+        ``p_thresh_spec`` (0.05).  Adds, with p_j = p_dla pi_j over the level-1 samples of a spectrum,
+
+        ``population_p_dlas`` (Q)               the p_dla the device formed from the evidences and the priors
+        ``population_poisson`` (Q x nz x nn)    per bin, sum of p_j with p_thresh_sample < p_j < p_switch
+        ``population_large_inds`` / ``_probs`` / ``_bins`` (Q x 8)   the samples with p_j >= p_switch in a bin,
+                                                 by increasing index (0-based), p_j and bin iz nn + in; unused
+                                                 slots -1 / NaN / -1
+        ``population=None`` is ``process_models``, bit for bit.  Repeated calls and any ``max_batch_spectra``
+        give bitwise equal outputs."""
+        pop = None
+        if population is not None:
+            known = {"z_edges", "log_nhi_edges", "log_nhi_samples", "log_priors_no_dla", "log_priors_dla",
+                     "log_priors_lls", "p_thresh_sample", "p_switch", "p_thresh_spec"}
+            if not isinstance(population, dict) or set(population) - known:
+                raise ValueError(f"population must be a dict of {sorted(known)}")
+            missing = {"z_edges", "log_nhi_edges", "log_nhi_samples", "log_priors_no_dla", "log_priors_dla"} - set(population)
+            if missing:
+                raise ValueError(f"population lacks {sorted(missing)}")
+
+            def vec(key):
+                return None if population.get(key) is None else np.ascontiguousarray(population[key], dtype=np.float64).ravel()
+            lognhi = vec("log_nhi_samples")
+            if lognhi.size != self.num_samples:
+                raise ValueError("one log_nhi sample per engine sample")
+            lp_dla = np.ascontiguousarray(population["log_priors_dla"], dtype=np.float64)
+            if lp_dla.ndim == 1:
+                lp_dla = lp_dla[None]
+            pop = dict(log_nhi=lognhi, z_edges=vec("z_edges"), log_nhi_edges=vec("log_nhi_edges"),
+                       log_priors_no_dla=vec("log_priors_no_dla"), log_priors_dla=lp_dla, log_priors_lls=vec("log_priors_lls"),
+                       p_thresh_sample=float(population.get("p_thresh_sample", 1e-4)),
+                       p_switch=float(population.get("p_switch", 0.25)),
+                       p_thresh_spec=float(population.get("p_thresh_spec", 0.05)))
+            if pop["z_edges"].size < 1 or pop["log_nhi_edges"].size < 1:
+                raise ValueError("population edges must not be empty")
+        return self._process_models(packed, max_dlas, sub_dla, log_nhi_samples, z_edges, log_nhi_edges, sub_dla_log_nhi,
+                                    want_samples, "population", pop, kwargs)
+
+    def population_stats(self) -> dict:
+        """gpdla_engine_get_population_stats: cumulative ms and count of the population launches."""
+        ms, n = C.c_double(0.0), C.c_int64(0)
+        L.check(self.lib.gpdla_engine_get_population_stats(self._h, C.byref(ms), C.byref(n)))
+        return dict(population_ms=ms.value, population_launches=n.value)
 
     def model_stats(self) -> dict:
         """gpdla_engine_get_model_stats: cumulative ms / launches of the forest kernel, the sub-DLA sweeps and
@@ -557,6 +657,50 @@ def posterior_summary(log_likelihoods, offset_samples, log_nhi_samples, nhi_samp
                MAP_log_nhis=np.ascontiguousarray(mn[:, :, :Lc]))
     if planes is not None:
         out["bin_planes"] = planes
+    return out
+
+
+def population_split(log_likelihoods, offset_samples, log_nhi_samples, min_z, max_z, p_dlas, z_edges, log_nhi_edges,
+                     p_thresh_sample: float = 1e-4, p_switch: float = 0.25, device: int = 0) -> dict:
+    """The split kernel alone (gpdla_population_split_f64) on host arrays: ``log_likelihoods`` rows x S (level
+    1), ``min_z`` / ``max_z`` / ``p_dlas`` one per row.  Returns ``Engine.process_population``'s
+    ``population_poisson``, ``population_large_inds`` / ``_probs`` / ``_bins``."""
+    ll = np.ascontiguousarray(np.atleast_2d(log_likelihoods), dtype=np.float64)
+    if ll.ndim != 2:
+        raise ValueError("log_likelihoods must be rows x S")
+    rows, S = ll.shape
+    off = np.ascontiguousarray(offset_samples, dtype=np.float64).ravel()
+    lognhi = np.ascontiguousarray(log_nhi_samples, dtype=np.float64).ravel()
+    if not off.size == lognhi.size == S:
+        raise ValueError("sample arrays must have S entries")
+    zmin, zmax, p = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (rows,)))
+                     for v in (min_z, max_z, p_dlas))
+    ez = np.ascontiguousarray(z_edges, dtype=np.float64).ravel()
+    en = np.ascontiguousarray(log_nhi_edges, dtype=np.float64).ravel()
+    nz, nn = ez.size - 1, en.size - 1
+    spec = L.PopulationSpec(log_nhi_samples=L.ptr(lognhi), num_z_bins=nz, num_nhi_bins=nn, z_edges=L.ptr(ez),
+                            log_nhi_edges=L.ptr(en), p_thresh_sample=float(p_thresh_sample), p_switch=float(p_switch),
+                            p_thresh_spec=0.05, log_priors_no_dla=None, log_priors_dla=None, log_priors_lls=None)
+    NL = L.POPULATION_MAX_LARGE
+    plane = np.zeros((rows, max(nz, 1), max(nn, 1)))
+    inds, bins = np.full((rows, NL), -1, dtype=np.int32), np.full((rows, NL), -1, dtype=np.int32)
+    probs = np.full((rows, NL), np.nan)
+    L.check(L.load().gpdla_population_split_f64(
+        device, L.ptr(ll), rows, S, S, L.ptr(off), L.ptr(lognhi), L.ptr(zmin), L.ptr(zmax), L.ptr(p), C.byref(spec),
+        L.ptr(plane), L.ptr(inds, C.c_int32), L.ptr(probs), L.ptr(bins, C.c_int32)))
+    return dict(population_poisson=plane, population_large_inds=inds, population_large_probs=probs,
+                population_large_bins=bins)
+
+
+def poisson_binomial_pmf_csr(probs, offsets, device: int = 0) -> np.ndarray:
+    """gpdla_poisson_binomial_pmf_f64: the coefficients of prod_j (1 - p_j + p_j x) of every bin of a CSR
+    trial list, concatenated (bin b at ``offsets[b] + b``, ``n_b + 1`` values)."""
+    p = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+    o = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
+    if o.size < 1 or o[-1] != p.size:
+        raise ValueError("offsets must have nbins + 1 entries ending at len(probs)")
+    out = np.empty(p.size + o.size - 1)
+    L.check(L.load().gpdla_poisson_binomial_pmf_f64(device, L.ptr(p), L.ptr(o, C.c_int64), o.size - 1, L.ptr(out)))
     return out
 
 

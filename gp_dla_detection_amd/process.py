@@ -232,11 +232,72 @@ def _summary_grid(summaries):
     return np.ascontiguousarray(ez, dtype=np.float64).ravel(), np.ascontiguousarray(en, dtype=np.float64).ravel()
 
 
-def _compute_kwargs(max_dlas: int, summaries, save_samples: bool, sub=None, forest=None) -> dict:
+POPULATION_DEFAULTS = dict(p_thresh_sample=1e-4, p_switch=0.25)   # calc_cddf.py:47,50
+POPULATION_MAX_LARGE = 8     # include/gpdla.h GPDLA_POPULATION_MAX_LARGE
+POPULATION_MAX_BINS = 1024   # GPDLA_SUMMARY_MAX_BINS
+
+
+def _population_spec(population):
+    """``population`` of process_qsos -> None (off) or dict(z_edges, log_nhi_edges, p_thresh_sample, p_switch),
+    checked as the library checks them."""
+    if population is None or population is False:
+        return None
+    keys = {"z_edges", "log_nhi_edges"} | set(POPULATION_DEFAULTS)
+    if not isinstance(population, dict) or set(population) - keys:
+        raise ValueError(f"population must be None or a dict of {sorted(keys)}")
+    if "z_edges" not in population or "log_nhi_edges" not in population:
+        raise ValueError("population needs z_edges and log_nhi_edges")
+    pop = dict(POPULATION_DEFAULTS)
+    for key in POPULATION_DEFAULTS:
+        if key in population:
+            pop[key] = float(population[key])
+    for key in ("z_edges", "log_nhi_edges"):
+        e = np.ascontiguousarray(population[key], dtype=np.float64).ravel()
+        if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
+            raise ValueError(f"population {key} must be at least two finite, strictly increasing edges")
+        pop[key] = e
+    if (pop["z_edges"].size - 1) * (pop["log_nhi_edges"].size - 1) > POPULATION_MAX_BINS:
+        raise ValueError(f"population grid exceeds {POPULATION_MAX_BINS} bins")
+    if not (np.isfinite(pop["p_switch"]) and pop["p_switch"] >= 1.0 / POPULATION_MAX_LARGE):
+        raise ValueError(f"p_switch must be finite and >= 1/{POPULATION_MAX_LARGE}")
+    if not 0.0 <= pop["p_thresh_sample"] < pop["p_switch"]:
+        raise ValueError("p_thresh_sample must lie in [0, p_switch)")
+    return pop
+
+
+def _model_log_priors(z_qsos, prior: dict | None, params: Parameters, max_dlas: int, sub=None):
+    """The log priors ``_finish`` will write, before the compute call (they depend on z_QSO and the prior
+    catalogue alone): (log_priors_no_dla [Q], log_priors_dla [D x Q], log_priors_lls [Q] or None), by the same
+    expressions as ``_finish`` / ``_finish_multi`` / ``_finish_sub``."""
+    Q, D = np.asarray(z_qsos).size, int(max_dlas)
+    if prior is not None:
+        dla_ind = filter_prior_dlas(prior["z_qsos"], prior["dla_ind"], prior.get("z_dlas", [None] * len(prior["z_qsos"])))
+        if D > 1:
+            lp_no, lp_dla = multi_dla_priors(z_qsos, prior["z_qsos"], dla_ind, D, params.prior_z_qso_increase)
+        else:
+            lp_no, lp_dla = dla_priors(z_qsos, prior["z_qsos"], dla_ind, params.prior_z_qso_increase)
+            lp_dla = lp_dla[:, None]
+        p = np.exp(dla_priors(z_qsos, prior["z_qsos"], dla_ind, params.prior_z_qso_increase)[1])
+    elif D > 1:
+        lp_no = np.full(Q, np.log(1 - 0.5))
+        lp_dla = np.tile(np.log([0.5 ** d - 0.5 ** (d + 1) for d in range(1, D)] + [0.5 ** D]), (Q, 1))
+        p = np.full(Q, 0.5)
+    else:
+        lp_no, lp_dla, p = np.full(Q, np.log(0.5)), np.full((Q, 1), np.log(0.5)), np.full(Q, 0.5)
+    lp_lls = None
+    if sub is not None:
+        lp_no, lp_lls = sub_dla_priors(p, sub["ratio"])
+    return lp_no, np.ascontiguousarray(np.asarray(lp_dla, dtype=np.float64).T), lp_lls
+
+
+def _compute_kwargs(max_dlas: int, summaries, save_samples: bool, sub=None, forest=None, population=None) -> dict:
     """What a ``compute`` replacement is told beyond the five positional arguments: only what differs
     from the plain single-DLA call, so existing replacements keep working.  ``sub_dla`` is the normalised
-    dict(nhi, log_nhi, ratio), ``forest`` the full settings dict."""
+    dict(nhi, log_nhi, ratio), ``forest`` the full settings dict, ``population`` the normalised dict of
+    ``_population_spec`` with the log priors of ``_model_log_priors`` added."""
     kw = {}
+    if population is not None:
+        kw["population"] = population
     if sub is not None:
         kw["sub_dla"] = sub
     if forest is not None:
@@ -252,18 +313,34 @@ def _compute_kwargs(max_dlas: int, summaries, save_samples: bool, sub=None, fore
 
 def _engine_compute(model: dict, samples: dict, packed: dict, params: Parameters, device: int = 0,
                     engine: Engine | None = None, max_dlas: int = 1, summaries=None, save_samples: bool = True,
-                    timings: dict | None = None, sub_dla=None, forest=None) -> dict:
+                    timings: dict | None = None, sub_dla=None, forest=None, population=None) -> dict:
     """The hot path on the GPU: per-spectrum null / sample / DLA log likelihoods and z ranges; with
     ``max_dlas`` > 1 every level of the multi-DLA search (Engine.process_multi's arrays); with
     ``summaries`` the posterior summaries as well (Engine.process_summaries), the sample arrays only if
     ``save_samples``.  ``sub_dla`` (the normalised dict of ``_sub_dla_spec``) adds the sub-DLA model's arrays
     (Engine.process_models); ``forest`` (the settings dict) is set on the engine for this call and cleared
-    after it."""
+    after it.  ``population`` (the dict ``_compute_kwargs`` documents) adds Engine.process_population's arrays."""
     grid = _summary_grid(summaries)
     eng = engine or Engine(model, samples, params, device=device)
     try:
         if forest is not None:
             eng.set_forest(forest)
+        if population is not None:
+            if "log_nhi_samples" not in samples:
+                raise ValueError("population needs samples['log_nhi_samples']")
+            res = eng.process_population(
+                packed, max_dlas, population=dict(population, log_nhi_samples=samples["log_nhi_samples"]),
+                sub_dla=None if sub_dla is None else sub_dla["nhi"],
+                log_nhi_samples=samples["log_nhi_samples"] if grid is not None else None,
+                z_edges=grid[0] if grid is not None else None, log_nhi_edges=grid[1] if grid is not None else None,
+                sub_dla_log_nhi=None if sub_dla is None else sub_dla["log_nhi"], want_samples=save_samples)
+            if max_dlas == 1:   # Engine.process's shapes: no level axis, no multi-DLA variables
+                res["log_likelihoods_dla"] = res["log_likelihoods_dla"][0]
+                if "sample_log_likelihoods_dla" in res:
+                    res["sample_log_likelihoods_dla"] = res["sample_log_likelihoods_dla"][0]
+                res.pop("base_sample_inds", None)
+                res.pop("max_dlas", None)
+            return res
         if sub_dla is not None:
             if grid is not None and "log_nhi_samples" not in samples:
                 raise ValueError("summaries need samples['log_nhi_samples']")
@@ -395,6 +472,28 @@ def _finish_sub(out: dict, res: dict, z_qsos, prior: dict | None, params: Parame
     return out
 
 
+def _finish_population(out: dict, res: dict, pop: dict) -> dict:
+    """Add POPULATION_VARIABLES to the saved ones.  ``res`` holds Engine.process_population's arrays; the
+    sample indices and the flat bins (iz nn + in) become 1-based doubles with 0 = none, like
+    ``base_sample_inds``."""
+    Q = np.asarray(out["log_likelihoods_no_dla"]).size
+    nz, nn = pop["z_edges"].size - 1, pop["log_nhi_edges"].size - 1
+    plane = np.asarray(res["population_poisson"], dtype=np.float64)
+    if plane.shape != (Q, nz, nn):
+        raise ValueError(f"population_poisson must be {(Q, nz, nn)}")
+    out["population_poisson"] = plane
+    for key in ("population_large_inds", "population_large_bins"):
+        v = np.asarray(res[key])
+        if v.shape != (Q, POPULATION_MAX_LARGE):
+            raise ValueError(f"{key} must be {(Q, POPULATION_MAX_LARGE)}")
+        out[key] = v.astype(np.float64) + 1.0
+    out["population_large_probs"] = np.asarray(res["population_large_probs"], dtype=np.float64)
+    out["population_p_dlas"] = np.asarray(res["population_p_dlas"], dtype=np.float64)
+    out["population_z_edges"], out["population_log_nhi_edges"] = pop["z_edges"], pop["log_nhi_edges"]
+    out["population_p_thresh_sample"], out["population_p_switch"] = pop["p_thresh_sample"], pop["p_switch"]
+    return out
+
+
 def _finish(res: dict, z_qsos, prior: dict | None, params: Parameters, metadata: dict | None,
             max_dlas: int = 1, summaries=None, sub=None, forest=None) -> dict:
     """process_qsos.m:122-132, 150-155, 202-232: priors, posteriors and the saved scalars."""
@@ -439,7 +538,7 @@ def _finish(res: dict, z_qsos, prior: dict | None, params: Parameters, metadata:
 def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
                  params: Parameters | None = None, test_ind=None, engine: Engine | None = None,
                  device: int = 0, metadata: dict | None = None, max_dlas: int = 1, compute=None,
-                 summaries=None, save_samples: bool = True, sub_dla=None, forest=None) -> dict:
+                 summaries=None, save_samples: bool = True, sub_dla=None, forest=None, population=None) -> dict:
     """Run the DLA search (process_qsos.m:88-232) and return the saved variables.  ``max_dlas`` > 1
     (up to 4) runs the multi-DLA search: ``log_likelihoods_dla`` / ``log_priors_dla`` /
     ``log_posteriors_dla`` become Q x D, ``model_posteriors`` Q x (1 + D), ``sample_log_likelihoods_dla``
@@ -464,21 +563,37 @@ def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
     (``variance_series``) and suppress mu by the mean flux (``mean_flux``), for every model; the output
     records FOREST_VARIABLES.  Both run on the fused fp64 path only; without them every variable is as
     before, bit for bit.  A ``compute`` replacement receives ``sub_dla=`` (dict(nhi, log_nhi, ratio)) and
-    ``forest=`` (the full settings) when they are set."""
+    ``forest=`` (the full settings) when they are set.
+
+    ``population`` (``dict(z_edges=..., log_nhi_edges=..., p_thresh_sample=1e-4, p_switch=0.25)``) has the
+    engine reduce what the reference's confidence intervals need (calc_cddf.py ``_split_distributions_single``;
+    Engine.process_population): the priors are then computed before the compute call and handed to it, and the
+    output gains POPULATION_VARIABLES (catalog.py's ``split_distributions`` and the functions after it consume
+    them).  It combines with every other keyword; without it every variable is as before, bit for bit.  A
+    ``compute`` replacement receives ``population=`` (the edges, the thresholds and ``log_priors_no_dla`` [Q],
+    ``log_priors_dla`` [D x Q], ``log_priors_lls`` [Q] or None) only when it is set."""
     if not 1 <= int(max_dlas) <= 4:
         raise ValueError("max_dlas must be 1..4")
+    pop = _population_spec(population)
     params = params or set_parameters(k=np.asarray(model["M"]).shape[1])
     sub, fst = _sub_dla_spec(sub_dla, samples, device), _forest_spec(forest)
     packed = _select(spectra, test_ind)
+    popkw = None
+    if pop is not None:
+        lp_no, lp_dla, lp_lls = _model_log_priors(packed["z_qsos"], prior, params, max_dlas, sub)
+        popkw = dict(pop, log_priors_no_dla=lp_no, log_priors_dla=lp_dla, log_priors_lls=lp_lls)
     if compute is not None:
-        res = compute(model, samples, packed, params, device, **_compute_kwargs(max_dlas, summaries, save_samples, sub, fst))
+        res = compute(model, samples, packed, params, device,
+                      **_compute_kwargs(max_dlas, summaries, save_samples, sub, fst, popkw))
     else:
         res = _engine_compute(model, samples, packed, params, device, engine, max_dlas, summaries, save_samples,
-                              sub_dla=sub, forest=fst)
+                              sub_dla=sub, forest=fst, population=popkw)
     if not save_samples:
         res = {k: v for k, v in res.items() if k not in ("sample_log_likelihoods_dla", "base_sample_inds",
                                                          "sample_log_likelihoods_lls")}
     out = _finish(res, packed["z_qsos"], prior, params, metadata, max_dlas, summaries, sub, fst)
+    if pop is not None:
+        _finish_population(out, res, pop)
     if test_ind is not None:
         out["test_ind"] = np.asarray(test_ind)
     return out
@@ -504,6 +619,10 @@ SUB_DLA_VARIABLES = ("log_priors_lls", "log_likelihoods_lls", "log_posteriors_ll
 # what a run with the Lyman-series forest records (process_qsos(forest=...))
 FOREST_VARIABLES = ("num_forest_lines", "forest_variance_series", "forest_mean_flux", "mean_flux_tau_0",
                     "mean_flux_beta")
+# what a run with the population statistics saves besides (process_qsos(population=...)); catalog.py reads them
+POPULATION_VARIABLES = ("population_poisson", "population_large_inds", "population_large_probs",
+                        "population_large_bins", "population_p_dlas", "population_z_edges",
+                        "population_log_nhi_edges", "population_p_thresh_sample", "population_p_switch")
 
 
 def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
@@ -525,11 +644,11 @@ def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
     has no sample array (and no ``base_sample_inds``) to write.  A run with ``sub_dla`` writes the
     SUB_DLA_VARIABLES (``model_posteriors`` is then Q x (1 + D + 1), the sub-DLA column last, so h5py's
     ``model_posteriors[2]`` still reads "exactly two DLAs", calc_cddf.py:67), one with ``forest`` the
-    FOREST_VARIABLES."""
+    FOREST_VARIABLES, one with ``population`` the POPULATION_VARIABLES."""
     mat = {}
     multi = int(np.ravel(out.get("max_dlas", 1))[0]) > 1
     for key in (PROCESSED_VARIABLES + (MULTI_DLA_VARIABLES if multi else ()) + SUMMARY_VARIABLES + SUB_DLA_VARIABLES +
-                FOREST_VARIABLES):
+                FOREST_VARIABLES + POPULATION_VARIABLES):
         if key not in out:
             continue
         v = out[key]
@@ -686,7 +805,7 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
                      params: Parameters | None = None, device: int = 0, save: bool = True,
                      rank: int = 0, world: int = 1, compute=None, timings: dict | None = None,
                      chunk_rows: int | None = None, max_dlas: int = 1, summaries=None,
-                     save_samples: bool = True, sub_dla=None, forest=None) -> dict:
+                     save_samples: bool = True, sub_dla=None, forest=None, population=None) -> dict:
     """The whole ``process_qsos`` script (process_qsos.m:1-249) on files laid out as the reference
     lays them out (set_parameters.m:79-86):
 
@@ -722,10 +841,14 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
     with ``save_samples=False``, no sample array), on one GPU only as well.
     ``sub_dla`` / ``forest`` as in ``process_qsos``: ``sub_dla`` on one GPU only (``world`` > 1 raises
     NotImplementedError: its arrays are not gathered); ``forest`` alone passes through to every rank's
-    engine."""
+    engine.  ``population`` as in ``process_qsos``, on one GPU only (``world`` > 1 raises NotImplementedError:
+    its arrays are not gathered)."""
     import time
     if not 1 <= int(max_dlas) <= 4:
         raise ValueError("max_dlas must be 1..4")
+    pop = _population_spec(population)
+    if pop is not None and world > 1:
+        raise NotImplementedError("population with world > 1: the population arrays are not gathered")
     if max_dlas > 1 and world > 1:
         raise NotImplementedError("max_dlas > 1 with world > 1: the sharded writer takes the 2-D sample array only")
     if (_summary_grid(summaries) is not None or not save_samples) and world > 1:
@@ -771,6 +894,10 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
     mine = shards[rank]
     packed = load_preloaded_qsos_packed(f"{rdir}/preloaded_qsos.mat", tidx[mine])
     packed["z_qsos"] = np.ascontiguousarray(z_all[mine], dtype=np.float64)
+    popkw = None
+    if pop is not None:
+        lp_no, lp_dla, lp_lls = _model_log_priors(z_all[mine], dict(z_qsos=pz, dla_ind=pdla, z_dlas=pzd), params, max_dlas, sub)
+        popkw = dict(pop, log_priors_no_dla=lp_no, log_priors_dla=lp_dla, log_priors_lls=lp_lls)
     t_load = time.perf_counter()
     tm["load_s"] = t_load - t_start
     if compute is _engine_compute:  # the compute phase split: engine creation, then the batches
@@ -778,11 +905,12 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
         tm["engine_create_s"] = time.perf_counter() - t_load
         try:
             res = _engine_compute(model, samples, packed, params, device, eng, max_dlas, summaries, save_samples,
-                                  timings=tm, sub_dla=sub, forest=fst)
+                                  timings=tm, sub_dla=sub, forest=fst, population=popkw)
         finally:
             eng.close()
     else:
-        res = compute(model, samples, packed, params, device, **_compute_kwargs(max_dlas, summaries, save_samples, sub, fst))
+        res = compute(model, samples, packed, params, device,
+                      **_compute_kwargs(max_dlas, summaries, save_samples, sub, fst, popkw))
     if not save_samples:
         res = {k: v for k, v in res.items() if k not in ("sample_log_likelihoods_dla", "base_sample_inds",
                                                          "sample_log_likelihoods_lls")}
@@ -795,6 +923,8 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
     path = f"{rdir}/processed_qsos_{test_set_name}.mat"
     if world == 1:
         out = _finish(res, z_all, prior, params, meta, max_dlas, summaries, sub, fst)
+        if pop is not None:
+            _finish_population(out, res, pop)
         out["test_ind"] = tind
         if save:
             save_processed_qsos(path, out)

@@ -365,6 +365,79 @@ typedef struct gpdla_model_stats {
 } gpdla_model_stats;
 int gpdla_engine_get_model_stats(gpdla_engine* engine, gpdla_model_stats* stats);
 
+/* ---- Population statistics (CDDF_analysis/calc_cddf.py) -----------------------
+ * What the reference's confidence intervals on f(N), dN/dX and Omega_DLA need from the level-1 sample
+ * rows (_split_distributions_single, calc_cddf.py:724-778), reduced per device batch after its last
+ * level.  With pi_j the normalised level-1 masses exactly as the summaries form them and p_dla the
+ * spectrum's posterior probability of at least one DLA, p_j = p_dla pi_j, and sample j belongs to a bin
+ * of the spec's own (z, log N_HI) grid by the summaries' rule (half-open, z with separately rounded
+ * product and sum; samples outside belong to no bin).  Per spectrum q:
+ *   poisson_plane   per bin, the sum of p_j over its samples with p_thresh_sample < p_j < p_switch, added
+ *                   in sample-index order
+ *   large_*         the samples with p_j >= p_switch that fall in some bin, by increasing sample index:
+ *                   index (0-based), p_j and bin (iz num_nhi_bins + in); unused slots -1 / NaN / -1
+ *   p_dlas          the p_dla used: formed on the device from the evidences and the spec's log priors as
+ *                   exp(lp_m - max) / sum over the models no-DLA, DLA levels 1..D (a NaN evidence at a
+ *                   level >= 2 counts as -inf) and, with the sub-DLA model, sub-DLA;
+ *                   p_dla = 1 - p_no (- p_sub).  NaN when a posterior is NaN: such a row gives zeros.
+ * sum pi = 1 bounds the large samples by 1 / p_switch, hence p_switch >= 1 / GPDLA_POPULATION_MAX_LARGE.
+ * Every output is a fixed-order reduction: repeated calls and any split into device batches agree bit
+ * for bit. */
+#define GPDLA_POPULATION_MAX_LARGE 8
+typedef struct gpdla_population_spec {
+  const double* log_nhi_samples;     /* host [S]; not read by gpdla_population_split_f64 */
+  int32_t num_z_bins, num_nhi_bins;  /* nz, nn >= 1 with nz nn <= GPDLA_SUMMARY_MAX_BINS */
+  const double* z_edges;             /* host [nz + 1], absolute redshift, finite, strictly increasing */
+  const double* log_nhi_edges;       /* host [nn + 1], likewise */
+  double p_thresh_sample;            /* in [0, p_switch) (calc_cddf.py:47: 1e-4) */
+  double p_switch;                   /* >= 1 / GPDLA_POPULATION_MAX_LARGE (calc_cddf.py:50: 0.25) */
+  double p_thresh_spec;              /* recorded for the host stage (calc_cddf.py:45: 0.05); not applied here */
+  /* log priors, host; read by gpdla_engine_process_population only */
+  const double* log_priors_no_dla;   /* [Q] */
+  const double* log_priors_dla;      /* [D][Q] */
+  const double* log_priors_lls;      /* [Q]; required with the sub-DLA model */
+} gpdla_population_spec;
+
+typedef struct gpdla_population {
+  int32_t memory;                    /* GPDLA_MEM_HOST or GPDLA_MEM_DEVICE */
+  double* poisson_plane;             /* [Q][nz][nn] */
+  int32_t* large_inds;               /* [Q][GPDLA_POPULATION_MAX_LARGE] */
+  double* large_probs;               /* [Q][GPDLA_POPULATION_MAX_LARGE] */
+  int32_t* large_bins;               /* [Q][GPDLA_POPULATION_MAX_LARGE] */
+  double* p_dlas;                    /* [Q] */
+} gpdla_population;
+
+/* gpdla_engine_process_models plus the population outputs; with pspec and population both NULL it is
+ * that call, bit for bit, and with them every other result is unchanged bit for bit.  GPDLA_EINVAL for
+ * one of the two NULL and the other not, a null array, a malformed grid, p_switch < 1 /
+ * GPDLA_POPULATION_MAX_LARGE or p_thresh_sample outside [0, p_switch). */
+int gpdla_engine_process_population(gpdla_engine* engine, const gpdla_spectra* spectra,
+                                    const gpdla_multi_dla* multi, const gpdla_sub_dla* sub,
+                                    const gpdla_results_multi* results_multi, const gpdla_results_sub* results_sub,
+                                    const gpdla_summary_spec* spec, const gpdla_summaries* summaries,
+                                    const gpdla_population_spec* pspec, const gpdla_population* population);
+/* Cumulative kernel time (HIP events) and count of the population launches (the posterior and the split
+ * launch of a batch are one span) since create / reset_stats. */
+int gpdla_engine_get_population_stats(gpdla_engine* engine, double* ms, int64_t* launches);
+/* The split kernel alone, host buffers: ll [rows][ld] (ld >= S), the samples in the rows' order, min_z /
+ * max_z / p_dlas [rows] (p_dlas in [0, 1] or NaN).  Outputs as in gpdla_population with Q = rows. */
+int gpdla_population_split_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
+                               const double* offset_samples, const double* log_nhi_samples, const double* min_z,
+                               const double* max_z, const double* p_dlas, const gpdla_population_spec* spec,
+                               double* poisson_plane, int32_t* large_inds, double* large_probs, int32_t* large_bins);
+/* Poisson-binomial pmf of num_bins trial lists in CSR form (host buffers): bin b holds the probabilities
+ * probs[offsets[b] .. offsets[b + 1]) (offsets[0] = 0, n_b <= GPDLA_PMF_MAX_TRIALS each) and receives the
+ * n_b + 1 coefficients of prod_j (1 - p_j + p_j x) at pmf[offsets[b] + b ...]; n_b = 0 gives [1.0].  A
+ * product of polynomials with non-negative coefficients (no DFT): chunks of GPDLA_PMF_CHUNK trials by the
+ * recurrence pmf[k] <- pmf[k] (1 - p) + pmf[k - 1] p, folded left to right by convolution, so every
+ * coefficient above the smallest normal is within a relative 4 (n_b + 1) 2^-53 of the exact one and a
+ * bin's result does not depend on the other bins of the call.  GPDLA_EINVAL for a probability outside
+ * [0, 1] or non-finite.  gpdla_last_call_kernel_ms then reports 2 spans: the chunk launch, the folds. */
+#define GPDLA_PMF_CHUNK 512
+#define GPDLA_PMF_MAX_TRIALS (1 << 18)
+int gpdla_poisson_binomial_pmf_f64(int32_t device, const double* probs, const int64_t* offsets, int64_t num_bins,
+                                   double* pmf);
+
 /* voigt MEX replacement (voigt.c:253-304).  Host buffers.  out has n_padded - 6 values. */
 int gpdla_voigt_f64(const double* lambdas, int64_t n_padded, double z, double N,
                     int32_t num_lines, double* out);
@@ -475,9 +548,9 @@ int32_t gpdla_device_count(void);
  * (the multi-GPU bench reports it per rank; process_qsos.m:88's spectra loop split over devices). */
 int gpdla_device_pci_bus_id(int32_t device, char* buf, int32_t len);
 /* Kernel times (ms, HIP events) of the calling thread's last call of gpdla_read_spec_f32,
- * gpdla_preload_qsos_f32, gpdla_halton_rr2_f64 or gpdla_generate_dla_samples_f64, one per launch in
- * launch order: read_spec 1; preload_qsos 3 (range keys, scan, write); halton 1; generate 3 (KDE,
- * Halton, inverse CDF).  *count = launches recorded (0 for an empty call); at most capacity copied. */
+ * gpdla_preload_qsos_f32, gpdla_halton_rr2_f64, gpdla_generate_dla_samples_f64 or
+ * gpdla_poisson_binomial_pmf_f64, one per launch in launch order: read_spec 1; preload_qsos 3 (range
+ * keys, scan, write); halton 1; generate 3 (KDE, Halton, inverse CDF); pmf 2 (chunks, all fold steps).  *count = launches recorded (0 for an empty call); at most capacity copied. */
 int gpdla_last_call_kernel_ms(double* ms, int32_t capacity, int32_t* count);
 
 #ifdef __cplusplus
