@@ -203,6 +203,11 @@ SIGNATURES = {
     "gpdla_objective_destroy": (None, [C.c_void_p]),
     "gpdla_spectrum_loss_f64": (C.c_int, [dp, dp, dp, dp, dp, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                           C.c_double, dp, dp, dp, dp, dp, dp]),
+    "gpdla_objective_set_forest": (C.c_int, [C.c_void_p, dp, C.c_int32, C.c_int32]),
+    "gpdla_spectrum_loss_forest_f64": (C.c_int, [dp, dp, dp, dp, dp, C.c_int64, C.c_int32, C.c_double, C.c_double,
+                                                 C.c_double, C.c_double, C.c_int32, dp, dp, dp, dp, dp, dp]),
+    "gpdla_forest_rows_f64": (C.c_int, [C.c_int32, dp, dp, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32,
+                                        dp]),
     "gpdla_halton_rr2_f64": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int32, dp]),
     "gpdla_generate_dla_samples_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.POINTER(DlaPrior), dp, dp, dp,
                                                  dp]),

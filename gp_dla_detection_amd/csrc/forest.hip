@@ -4,46 +4,20 @@
 // with lambda_i = kTransitionWavelengths[i-1] 1e8 Angstrom and c_i = kLeadingConstants[i-1] /
 // kLeadingConstants[0] (= f_i lambda_i / (f_1 lambda_1)), summed in line order.  forest_kernel runs
 // between prep_kernel and the likelihood sweep and rewrites the kMu / kOmega2 words of the valid
-// slots of the fused layout; forest_f64_kernel is the same sum on a plain wavelength array.
+// slots of the fused layout; forest_f64_kernel is the same sum on a plain wavelength array.  The sum
+// itself (forest_tables, forest_tau) is forest_series.h's, which the training objective shares.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 
 #include "device_common.h"
+#include "forest_series.h"
 #include "internal.h"
 
 namespace gpdla {
 
 namespace {
-
-// lambda_i (Angstrom) and c_i into LDS: one multiplication / one division each, correctly rounded,
-// i.e. the doubles a host restatement gets from the same two tables
-__device__ inline void forest_tables(double* s_lam, double* s_c) {
-  if (threadIdx.x < kMaxLines) {
-    s_lam[threadIdx.x] = kTransitionWavelengths[threadIdx.x] * 1e8;
-    s_c[threadIdx.x] = kLeadingConstants[threadIdx.x] / kLeadingConstants[0];
-  }
-  __syncthreads();
-}
-
-// sum_i t_i(tau_0, beta) at observed wavelength lam.  The comparison and 1 + z_i are evaluated as
-// written (no contraction): a pixel one ulp either side of a line's edge must take the side the
-// model's definition gives it.
-__device__ inline double forest_tau(double lam, double z_qso, double tau_0, double beta, int L,
-                                    const double* s_lam, const double* s_c) {
-#pragma clang fp contract(off)
-  double sum = 0.0;
-  for (int i = 0; i < L; ++i) {
-    const double li = s_lam[i];
-    const double zi = (lam - li) / li;
-    if (zi <= z_qso) {
-      const double base = 1.0 + zi;
-      sum += tau_0 * s_c[i] * pow(base, beta);
-    }
-  }
-  return sum;
-}
 
 // One thread per slot; gridDim.y blocks share a spectrum's slots.  Slot j holds segment j / Ls, step
 // j % Ls, i.e. pixel-order position gg L + t (prep_kernel pass 3a); masked, padding and round-up

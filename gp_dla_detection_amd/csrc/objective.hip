@@ -19,11 +19,13 @@
 
 #include <cmath>
 #include <cstdint>
+#include <algorithm>
 #include <cstdlib>
 #include <vector>
 
 #include "../../include/gpdla.h"
 #include "device_common.h"
+#include "forest_series.h"
 #include "internal.h"
 
 namespace gpdla {
@@ -161,6 +163,114 @@ __global__ __launch_bounds__(kObjThreads) void objective_pixel_kernel(ObjArgs a)
   if (tid == 0) {
     a.part_s[q * kObjScalars + 4] = cnt;
     a.part_s[q * kObjScalars + 6] = logd;
+  }
+}
+
+// The Lyman-series forest in the objective
+struct ObjForestArgs {
+  const double* z_qsos;      // [Q] of the launch's first spectrum on (the batch offset q0 is applied by obj_run)
+  int32_t L;                 // 1..kMaxLines
+};
+
+// pass 1 with the series summed in the variance (Ho, Bird & Garnett 2020): objective_pixel_kernel with
+//   tau = sum_{i <= L} t_i,  t_i = tau_0 c_i (1 + z_i)^beta [z_i <= z_QSO]
+// at lambda = lya_1pz lambda_1 (forest_series.h), and the beta plane from sum_i t_i log(1 + z_i).  Same
+// outputs, same exclusion of NaN pixels; a pixel redward of Lya has no active line: tau = 0, sf = c_0 and
+// zero tau_0 / beta planes.
+// The sums are not taken line by line (up to L pow and log per pixel: measured, that kernel was the
+// largest launch of the evaluation).  1 + z_i = lya r_i with r_i = lambda_1 / lambda_i, and the active
+// lines are a prefix of the series (forest_active_lines, the shared comparison), so
+//   sum_i t_i = tau_0 lya^beta C[n],   sum_i t_i log(1 + z_i) = tau_0 lya^beta (log(lya) C[n] + E[n])
+// with the block's cumulative tables C[n] = sum_{i < n} c_i r_i^beta, E[n] = sum_{i < n} c_i r_i^beta log r_i:
+// one pow and one log per pixel.
+__global__ __launch_bounds__(kObjThreads) void objective_pixel_forest_kernel(ObjArgs a, ObjForestArgs f) {
+  __shared__ double red[8];
+  __shared__ double s_lam[kMaxLines], s_c[kMaxLines];
+  __shared__ double s_C[kMaxLines + 1], s_E[kMaxLines + 1];
+  const int P = a.P;
+  const int tid = threadIdx.x;
+  const int64_t q = blockIdx.x;
+  const int L = f.L;
+  forest_tables(s_lam, s_c);
+  // c_i r_i^beta and its log r_i multiple per line, then the running sums in line order by one thread
+  if (tid < L) {
+    const double r = s_lam[0] / s_lam[tid];
+    const double cr = s_c[tid] * pow(r, a.beta);
+    s_C[tid + 1] = cr;
+    s_E[tid + 1] = cr * log(r);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double c = 0.0, e = 0.0;
+    s_C[0] = 0.0;
+    s_E[0] = 0.0;
+    for (int i = 1; i <= L; ++i) {
+      c += s_C[i];
+      e += s_E[i];
+      s_C[i] = c;
+      s_E[i] = e;
+    }
+  }
+  __syncthreads();
+  const double z_qso = f.z_qsos[q];
+  const double* y = a.y + q * a.ld;
+  const double* lya = a.lya_1pz + q * a.ld;
+  const double* nv = a.noise + q * a.ld;
+  double* wout = a.part_w + q * (int64_t)a.ldw;
+  double* tout = a.part_t + q * (int64_t)a.ldw;
+  double logd = 0.0, cnt = 0.0;
+  for (int i = tid; i < P; i += kObjThreads) {
+    const double yi = y[i];
+    const bool valid = !(yi != yi);                               // objective.m:43 ~isnan
+    double wi = 0.0, ti = 0.0;
+    if (valid) {
+      const double lyi = lya[i];
+      const double lam = forest_lambda(lyi, s_lam);
+      const int n = forest_active_lines(lam, z_qso, L, s_lam);
+      const double tp = a.tau_0 * pow(lyi, a.beta);
+      const double tau = n > 0 ? tp * s_C[n] : 0.0;                                   // sum_i t_i
+      const double tlog = n > 0 ? tp * fma(log(lyi), s_C[n], s_E[n]) : 0.0;           // sum_i t_i log(1 + z_i)
+      const double om2 = a.omega2[i];
+      const double absorb = exp(-tau);
+      const double sf = 1 - absorb + a.c_0;
+      const double an = om2 * (sf * sf);
+      const double d = nv[i] + an;
+      wi = 1.0 / d;
+      ti = wi * yi;
+      logd += log(d);
+      cnt += 1.0;
+      // the planes pass 6 reads: half of d an / d log (omega, c_0, tau_0, beta) each, the 1/2 of the
+      // likelihood folded in as in objective_pixel_kernel (spectrum_loss.m:62-73)
+      double* px = a.part_px + q * 4 * (int64_t)P + i;
+      const double da = om2 * sf * absorb;
+      px[0] = an;
+      px[P] = a.c_0 * om2 * sf;
+      px[2 * P] = da * tau;
+      px[3 * P] = da * a.beta * tlog;
+    }
+    wout[i] = wi;
+    tout[i] = ti;
+  }
+  logd = block_sum(logd, red);
+  cnt = block_sum(cnt, red);
+  if (tid == 0) {
+    a.part_s[q * kObjScalars + 4] = cnt;
+    a.part_s[q * kObjScalars + 6] = logd;
+  }
+}
+
+// sum_i t_i for a Q x P matrix of 1 + z_Lya (row q at z_qsos[q]), one block per row, by forest_tau: the
+// mean-flux step of the training preparation.  NaN in, NaN out.
+__global__ __launch_bounds__(256) void forest_rows_kernel(const double* __restrict__ lya, const double* __restrict__ z_qsos,
+                                                          int64_t P, double tau_0, double beta, int32_t L,
+                                                          double* __restrict__ out) {
+  __shared__ double s_lam[kMaxLines], s_c[kMaxLines];
+  forest_tables(s_lam, s_c);
+  const int64_t q = blockIdx.x;
+  const double z = z_qsos[q];
+  for (int64_t i = threadIdx.x; i < P; i += 256) {
+    const double l = lya[q * P + i];
+    out[q * P + i] = (l != l) ? l : forest_tau(forest_lambda(l, s_lam), z, tau_0, beta, L, s_lam, s_c);
   }
 }
 
@@ -708,6 +818,8 @@ struct gpdla_objective {
   double* tot = nullptr;      // [k P + P + kObjScalars]
   double* mt = nullptr;       // [4 ceil(P / 4)][obj_kp(obj_kb(k))] pixel-major M
   double* om2 = nullptr;      // [P] omega^2 of the evaluation's log omega
+  double* z_qsos = nullptr;   // [Q] gpdla_objective_set_forest's copy
+  int32_t L = 0;              // its series lines; 0 = the Lya-only objective
 };
 
 namespace {
@@ -766,7 +878,12 @@ int obj_run(gpdla_objective* o, const double* dM_src, const double* lo_src, cons
     a.part_s = o->part_s;
     a.part_px = o->part_px;
     const dim3 grid((unsigned)nq), blk(kObjThreads);
-    hipLaunchKernelGGL(objective_pixel_kernel, grid, blk, 0, o->stream, a);
+    if (o->L > 0) {
+      const ObjForestArgs fa{o->z_qsos + q0, o->L};
+      hipLaunchKernelGGL(objective_pixel_forest_kernel, grid, blk, 0, o->stream, a, fa);
+    } else {
+      hipLaunchKernelGGL(objective_pixel_kernel, grid, blk, 0, o->stream, a);
+    }
     ObjGramArgs gm{};
     gm.ldw = ldw;
     gm.nep = nep;
@@ -860,6 +977,7 @@ void gpdla_objective_destroy(gpdla_objective* o) {
   (void)hipFree(o->tot);
   (void)hipFree(o->mt);
   (void)hipFree(o->om2);
+  (void)hipFree(o->z_qsos);
   if (o->stream) (void)hipStreamDestroy(o->stream);
   delete o;
 }
@@ -963,15 +1081,58 @@ int gpdla_objective_eval(gpdla_objective* o, const double* x, double* f, double*
   return GPDLA_OK;
 }
 
-int gpdla_spectrum_loss_f64(const double* y, const double* lya_1pz, const double* noise_variance,
-                            const double* M, const double* omega2, int64_t n, int32_t k, double c_0,
-                            double tau_0, double beta, double* nlog_p, double* dM, double* dlog_omega,
-                            double* dlog_c_0, double* dlog_tau_0, double* dlog_beta) {
+int gpdla_objective_set_forest(gpdla_objective* o, const double* z_qsos, int32_t memory, int32_t num_forest_lines) {
+  if (!o) return set_error(GPDLA_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(o->device));
+  // no evaluation is in flight (each _eval ends synchronised): the old copy can go
+  if (!z_qsos) {
+    (void)hipFree(o->z_qsos);
+    o->z_qsos = nullptr;
+    o->L = 0;
+    return GPDLA_OK;
+  }
+  if (num_forest_lines < 1 || num_forest_lines > kMaxLines)
+    return set_error(GPDLA_EINVAL, "num_forest_lines=%d outside [1, %d]", num_forest_lines, kMaxLines);
+  if (memory != GPDLA_MEM_HOST && memory != GPDLA_MEM_DEVICE) return set_error(GPDLA_EINVAL, "bad memory kind");
+  std::vector<double> z((size_t)o->Q);
+  const size_t bytes = (size_t)o->Q * sizeof(double);
+  if (bytes) {
+    if (memory == GPDLA_MEM_DEVICE)
+      HIP_TRY(hipMemcpy(z.data(), z_qsos, bytes, hipMemcpyDeviceToHost));
+    else
+      std::copy(z_qsos, z_qsos + o->Q, z.begin());
+  }
+  for (int64_t q = 0; q < o->Q; ++q)
+    if (!std::isfinite(z[q])) return set_error(GPDLA_EINVAL, "z_qsos[%lld] = %g: must be finite", (long long)q, z[q]);
+  double* d = nullptr;
+  if (hipMalloc(&d, std::max(bytes, sizeof(double))) != hipSuccess)
+    return set_error(GPDLA_ENOMEM, "objective z_qsos allocation failed");
+  if (bytes && hipMemcpy(d, z.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    return set_error(GPDLA_EDEVICE, "objective z_qsos upload failed");
+  }
+  (void)hipFree(o->z_qsos);
+  o->z_qsos = d;
+  o->L = num_forest_lines;
+  return GPDLA_OK;
+}
+
+namespace {
+
+// spectrum_loss for one spectrum; z_qso != NULL sums num_forest_lines series lines in the variance
+int spectrum_loss_run(const double* y, const double* lya_1pz, const double* noise_variance, const double* M,
+                      const double* omega2, int64_t n, int32_t k, double c_0, double tau_0, double beta,
+                      const double* z_qso, int32_t num_forest_lines, double* nlog_p, double* dM,
+                      double* dlog_omega, double* dlog_c_0, double* dlog_tau_0, double* dlog_beta) {
   if (!y || !lya_1pz || !noise_variance || !M || !omega2 || !nlog_p)
     return set_error(GPDLA_EINVAL, "null argument");
   gpdla_objective* o = nullptr;
   int rc = gpdla_objective_create(0, 1, n, k, y, lya_1pz, noise_variance, GPDLA_MEM_HOST, &o);
   if (rc) return rc;
+  if (z_qso && (rc = gpdla_objective_set_forest(o, z_qso, GPDLA_MEM_HOST, num_forest_lines)) != GPDLA_OK) {
+    gpdla_objective_destroy(o);
+    return rc;
+  }
   double* dbuf = nullptr;
   std::vector<double> tot((size_t)(k + 1) * n + kObjScalars);
   auto run = [&]() -> int {
@@ -995,6 +1156,62 @@ int gpdla_spectrum_loss_f64(const double* y, const double* lya_1pz, const double
   if (dlog_beta) *dlog_beta = s[3];
   if (s[5] > 0) return set_error(GPDLA_ENUMERIC, "non-positive Cholesky pivot in spectrum_loss");
   return GPDLA_OK;
+}
+
+}  // namespace
+
+int gpdla_spectrum_loss_f64(const double* y, const double* lya_1pz, const double* noise_variance,
+                            const double* M, const double* omega2, int64_t n, int32_t k, double c_0,
+                            double tau_0, double beta, double* nlog_p, double* dM, double* dlog_omega,
+                            double* dlog_c_0, double* dlog_tau_0, double* dlog_beta) {
+  return spectrum_loss_run(y, lya_1pz, noise_variance, M, omega2, n, k, c_0, tau_0, beta, nullptr, 0, nlog_p, dM,
+                           dlog_omega, dlog_c_0, dlog_tau_0, dlog_beta);
+}
+
+int gpdla_spectrum_loss_forest_f64(const double* y, const double* lya_1pz, const double* noise_variance,
+                                   const double* M, const double* omega2, int64_t n, int32_t k, double c_0,
+                                   double tau_0, double beta, double z_qso, int32_t num_forest_lines,
+                                   double* nlog_p, double* dM, double* dlog_omega, double* dlog_c_0,
+                                   double* dlog_tau_0, double* dlog_beta) {
+  return spectrum_loss_run(y, lya_1pz, noise_variance, M, omega2, n, k, c_0, tau_0, beta, &z_qso, num_forest_lines,
+                           nlog_p, dM, dlog_omega, dlog_c_0, dlog_tau_0, dlog_beta);
+}
+
+int gpdla_forest_rows_f64(int32_t device, const double* lya_1pzs, const double* z_qsos, int64_t num_quasars,
+                          int64_t num_pixels, double tau_0, double beta, int32_t num_forest_lines, double* out) {
+  if (!lya_1pzs || !z_qsos || !out || num_quasars < 0 || num_pixels < 0)
+    return set_error(GPDLA_EINVAL, "null argument or negative shape");
+  if (num_forest_lines < 1 || num_forest_lines > kMaxLines)
+    return set_error(GPDLA_EINVAL, "num_forest_lines=%d outside [1, %d]", num_forest_lines, kMaxLines);
+  if (!(tau_0 >= 0.0 && tau_0 < INFINITY) || !std::isfinite(beta))
+    return set_error(GPDLA_EINVAL, "tau_0 = %g, beta = %g: must be finite, tau_0 >= 0", tau_0, beta);
+  if (num_quasars > INT32_MAX) return set_error(GPDLA_EINVAL, "num_quasars above 2^31 - 1");
+  for (int64_t q = 0; q < num_quasars; ++q)
+    if (!std::isfinite(z_qsos[q]))
+      return set_error(GPDLA_EINVAL, "z_qsos[%lld] = %g: must be finite", (long long)q, z_qsos[q]);
+  int rc = check_device(device);
+  if (rc) return rc;
+  if (num_quasars == 0 || num_pixels == 0) return GPDLA_OK;
+  HIP_TRY(hipSetDevice(device));
+  const size_t bytes = (size_t)num_quasars * num_pixels * sizeof(double), zbytes = (size_t)num_quasars * sizeof(double);
+  double *d_lya = nullptr, *d_z = nullptr, *d_out = nullptr;
+  auto run = [&]() -> int {
+    HIP_TRY(hipMalloc(&d_lya, bytes));
+    HIP_TRY(hipMalloc(&d_z, zbytes));
+    HIP_TRY(hipMalloc(&d_out, bytes));
+    HIP_TRY(hipMemcpy(d_lya, lya_1pzs, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_z, z_qsos, zbytes, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(forest_rows_kernel, dim3((unsigned)num_quasars), dim3(256), 0, nullptr, (const double*)d_lya,
+                       (const double*)d_z, num_pixels, tau_0, beta, num_forest_lines, d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost));
+    return GPDLA_OK;
+  };
+  rc = run();
+  (void)hipFree(d_lya);
+  (void)hipFree(d_z);
+  (void)hipFree(d_out);
+  return rc;
 }
 
 }  // extern "C"

@@ -20,6 +20,13 @@ minFunc (the reference's optimiser, a third-party MATLAB package, not vendored) 
 scipy's L-BFGS-B, the same method family with the same iteration/evaluation caps; its iterates
 differ from minFunc's, the objective and gradient it is driven by are the parity-checked ones.
 As in objective.m, the tau_0 / beta priors enter the gradient but not f (objective.m:59-71).
+
+``forest`` (None, True or a dict over ``process.FOREST_DEFAULTS``, what ``process_qsos`` takes) trains
+the null model ``process_qsos(..., forest=...)`` evaluates (Ho, Bird & Garnett 2020; DESIGN.md section
+16): ``variance_series`` sums the Lyman series in the objective's optical depth, per spectrum at its
+own z_QSO (``z_qsos`` / ``z_qso`` / ``num_forest_lines`` of ``Objective`` / ``objective`` /
+``spectrum_loss``); ``mean_flux`` divides Kim et al.'s mean flux out of the training fluxes before the
+mean is taken, so mu is the unabsorbed continuum the engine suppresses by the same factor.
 """
 from __future__ import annotations
 
@@ -32,8 +39,20 @@ from . import _lib as L
 from . import parameters as P
 
 
-def spectrum_loss(y, lya_1pz, noise_variance, M, omega2, c_0, tau_0, beta):
-    """``[nlog_p, dM, dlog_omega, dlog_c_0, dlog_tau_0, dlog_beta] = spectrum_loss(...)``."""
+def _forest_spec(forest):
+    from .process import _forest_spec as spec
+    return spec(forest)
+
+
+def _num_lines(num_forest_lines):
+    return 31 if num_forest_lines is None else int(num_forest_lines)
+
+
+def spectrum_loss(y, lya_1pz, noise_variance, M, omega2, c_0, tau_0, beta, z_qso=None, num_forest_lines=None):
+    """``[nlog_p, dM, dlog_omega, dlog_c_0, dlog_tau_0, dlog_beta] = spectrum_loss(...)``.  With ``z_qso`` the
+    optical depth sums ``num_forest_lines`` (default 31) Lyman-series lines (gpdla_spectrum_loss_forest_f64)."""
+    if z_qso is None and num_forest_lines is not None:
+        raise ValueError("spectrum_loss: num_forest_lines needs z_qso")
     lib = L.load()
     y = np.ascontiguousarray(y, dtype=np.float64).ravel()
     n = y.size
@@ -49,16 +68,24 @@ def spectrum_loss(y, lya_1pz, noise_variance, M, omega2, c_0, tau_0, beta):
     dM = np.empty(n * k)
     dlo = np.empty(n)
     sc = np.empty(3)
-    L.check(lib.gpdla_spectrum_loss_f64(L.ptr(y), L.ptr(lya), L.ptr(nv), L.ptr(Mf), L.ptr(om2), n, k,
-                                        float(c_0), float(tau_0), float(beta), L.ptr(nlp), L.ptr(dM),
-                                        L.ptr(dlo), L.ptr(sc[0:1]), L.ptr(sc[1:2]), L.ptr(sc[2:3])))
+    outs = (L.ptr(nlp), L.ptr(dM), L.ptr(dlo), L.ptr(sc[0:1]), L.ptr(sc[1:2]), L.ptr(sc[2:3]))
+    if z_qso is None:
+        L.check(lib.gpdla_spectrum_loss_f64(L.ptr(y), L.ptr(lya), L.ptr(nv), L.ptr(Mf), L.ptr(om2), n, k,
+                                            float(c_0), float(tau_0), float(beta), *outs))
+    else:
+        L.check(lib.gpdla_spectrum_loss_forest_f64(L.ptr(y), L.ptr(lya), L.ptr(nv), L.ptr(Mf), L.ptr(om2), n, k,
+                                                   float(c_0), float(tau_0), float(beta), float(z_qso),
+                                                   _num_lines(num_forest_lines), *outs))
     return float(nlp[0]), dM.reshape(n, k, order="F"), dlo, float(sc[0]), float(sc[1]), float(sc[2])
 
 
 class Objective:
-    """objective.m with the training matrices resident on ``device``: ``f, g = obj(x)``."""
+    """objective.m with the training matrices resident on ``device``: ``f, g = obj(x)``.  ``z_qsos`` (one
+    per spectrum) sums ``num_forest_lines`` (default 31) Lyman-series lines in the optical depth
+    (``set_forest``)."""
 
-    def __init__(self, centered_rest_fluxes, lya_1pzs, rest_noise_variances, k: int, device: int = 0):
+    def __init__(self, centered_rest_fluxes, lya_1pzs, rest_noise_variances, k: int, device: int = 0,
+                 z_qsos=None, num_forest_lines=None):
         self.lib = L.load()
         y = np.ascontiguousarray(centered_rest_fluxes, dtype=np.float64)
         lya = np.ascontiguousarray(lya_1pzs, dtype=np.float64)
@@ -73,6 +100,27 @@ class Objective:
                                                 L.ptr(lya), L.ptr(nv), L.MEM_HOST, C.byref(h)))
         self._h = h
         self.evaluations = 0
+        if z_qsos is not None:
+            self.set_forest(z_qsos, _num_lines(num_forest_lines))
+        elif num_forest_lines is not None:
+            self.close()
+            raise ValueError("Objective: num_forest_lines needs z_qsos")
+
+    def set_forest(self, z_qsos, num_forest_lines: int = 31, memory: int = L.MEM_HOST):
+        """gpdla_objective_set_forest: every later evaluation sums the series at these redshifts; ``None``
+        restores the Lya-only objective.  ``memory=MEM_DEVICE``: ``z_qsos`` is a raw device address of
+        num_quasars doubles (copied)."""
+        if z_qsos is None:
+            L.check(self.lib.gpdla_objective_set_forest(self._h, None, L.MEM_HOST, 0))
+            return
+        if memory == L.MEM_DEVICE:
+            p = L.dev_ptr(int(z_qsos))
+        else:
+            z = np.ascontiguousarray(z_qsos, dtype=np.float64).ravel()
+            if z.size != self.num_quasars:
+                raise ValueError(f"z_qsos has {z.size} entries, expected num_quasars = {self.num_quasars}")
+            p = L.ptr(z)
+        L.check(self.lib.gpdla_objective_set_forest(self._h, p, int(memory), int(num_forest_lines)))
 
     def __call__(self, x):
         x = np.ascontiguousarray(x, dtype=np.float64).ravel()
@@ -102,12 +150,14 @@ class Objective:
         self.close()
 
 
-def objective(x, centered_rest_fluxes, lya_1pzs, rest_noise_variances, device: int = 0):
-    """``[f, g] = objective(x, centered_rest_fluxes, lya_1pzs, rest_noise_variances)``."""
+def objective(x, centered_rest_fluxes, lya_1pzs, rest_noise_variances, device: int = 0, z_qsos=None,
+              num_forest_lines=None):
+    """``[f, g] = objective(x, centered_rest_fluxes, lya_1pzs, rest_noise_variances)``; ``z_qsos`` /
+    ``num_forest_lines`` as in ``Objective``."""
     x = np.asarray(x, dtype=np.float64).ravel()
     num_pixels = np.asarray(centered_rest_fluxes).shape[1]
     k = (x.size - 3) // num_pixels - 1                                      # objective.m:18
-    with Objective(centered_rest_fluxes, lya_1pzs, rest_noise_variances, k, device) as obj:
+    with Objective(centered_rest_fluxes, lya_1pzs, rest_noise_variances, k, device, z_qsos, num_forest_lines) as obj:
         return obj(x)
 
 
@@ -129,11 +179,27 @@ def _interp1(x, v, xq):
     return out
 
 
+def forest_rows(lya_1pzs, z_qsos, tau_0, beta, num_forest_lines=31, device: int = 0) -> np.ndarray:
+    """sum_i t_i(tau_0, beta) per entry of the (num_quasars, num_pixels) matrix of 1 + z_Lya, row q at
+    ``z_qsos[q]`` (gpdla_forest_rows_f64); NaN in, NaN out."""
+    lya = np.ascontiguousarray(lya_1pzs, dtype=np.float64)
+    z = np.ascontiguousarray(z_qsos, dtype=np.float64).ravel()
+    if lya.ndim != 2 or z.size != lya.shape[0]:
+        raise ValueError("forest_rows: lya_1pzs must be (num_quasars, num_pixels) with one z_qso per row")
+    out = np.empty_like(lya)
+    L.check(L.load().gpdla_forest_rows_f64(device, L.ptr(lya), L.ptr(z), lya.shape[0], lya.shape[1], float(tau_0),
+                                           float(beta), int(num_forest_lines), L.ptr(out)))
+    return out
+
+
 def prepare_training_data(spectra, z_qsos, max_noise_variance: float = P.MAX_NOISE_VARIANCE,
-                          rest_wavelengths=None):
+                          rest_wavelengths=None, forest=None, device: int = 0):
     """learn_qso_model.m:27-80 -> (rest_wavelengths, mu, centered_rest_fluxes, lya_1pzs,
     rest_noise_variances).  ``spectra``: dicts with wavelengths / flux / noise_variance /
-    pixel_mask (the preloaded_qsos cells selected by train_ind)."""
+    pixel_mask (the preloaded_qsos cells selected by train_ind).  With ``forest``'s ``mean_flux`` the
+    fluxes are divided by F = exp(-sum_i t_i(mean_flux_tau_0, mean_flux_beta)) and the noise variances
+    by F^2 between the noise cut (:71) and the mean (:77), on ``device``."""
+    forest = _forest_spec(forest)
     if rest_wavelengths is None:
         rest_wavelengths = np.arange(P.MIN_LAMBDA, P.MAX_LAMBDA + P.DLAMBDA / 2, P.DLAMBDA)   # :33
     R = rest_wavelengths.size
@@ -156,6 +222,11 @@ def prepare_training_data(spectra, z_qsos, max_noise_variance: float = P.MAX_NOI
     lya_1pzs[ind] = np.nan
     rest_fluxes[ind] = np.nan
     rest_noise_variances[ind] = np.nan
+    if forest is not None and forest["mean_flux"]:
+        F = np.exp(-forest_rows(lya_1pzs, z_qsos, forest["mean_flux_tau_0"], forest["mean_flux_beta"],
+                                forest["num_forest_lines"], device))
+        rest_fluxes = rest_fluxes / F
+        rest_noise_variances = rest_noise_variances / F ** 2
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", RuntimeWarning)       # all-NaN rest pixels -> NaN, as in MATLAB
         mu = np.nanmean(rest_fluxes, axis=0)                                  # :77
@@ -206,10 +277,14 @@ def initial_parameters(centered_rest_fluxes, k: int = P.K):
 
 
 def learn_qso_model(spectra, z_qsos, k: int = P.K, max_iter: int = 2000, max_fun_evals: int = 4000,
-                    device: int = 0) -> dict:
-    """learn_qso_model.m:27-131 on preloaded spectra; returns the saved variables."""
+                    device: int = 0, forest=None) -> dict:
+    """learn_qso_model.m:27-131 on preloaded spectra; returns the saved variables, with ``forest`` also
+    ``process.FOREST_VARIABLES`` (the settings the model was trained under)."""
     from scipy.optimize import minimize
-    rest_wavelengths, mu, centered, lya_1pzs, noise = prepare_training_data(spectra, z_qsos)
+    forest = _forest_spec(forest)
+    rest_wavelengths, mu, centered, lya_1pzs, noise = prepare_training_data(spectra, z_qsos, forest=forest,
+                                                                            device=device)
+    series = forest is not None and forest["variance_series"]
     x0, initial_M, initial_log_omega = initial_parameters(centered, k)
     R = rest_wavelengths.size
     # Rest pixels seen by fewer than two training spectra get log omega = -Inf / NaN from nanstd
@@ -220,12 +295,13 @@ def learn_qso_model(spectra, z_qsos, k: int = P.K, max_iter: int = 2000, max_fun
     if np.any(bad):
         lo[bad] = np.median(lo[~bad]) if np.any(~bad) else np.log(0.1)
     x0 = np.nan_to_num(x0, nan=0.0)
-    with Objective(centered, lya_1pzs, noise, k, device) as obj:
+    with Objective(centered, lya_1pzs, noise, k, device, z_qsos if series else None,
+                   forest["num_forest_lines"] if series else None) as obj:
         res = minimize(obj, x0, jac=True, method="L-BFGS-B",
                        options=dict(maxiter=max_iter, maxfun=max_fun_evals))
         evals = obj.evaluations
     x = res.x
-    return dict(rest_wavelengths=rest_wavelengths, mu=mu, initial_M=initial_M,
+    out = dict(rest_wavelengths=rest_wavelengths, mu=mu, initial_M=initial_M,
                 initial_log_omega=initial_log_omega, initial_log_c_0=np.log(P.INITIAL_C_0),
                 initial_tau_0=P.INITIAL_TAU_0, initial_beta=P.INITIAL_BETA,
                 M=x[:R * k].reshape(R, k, order="F"), log_omega=x[R * k:R * (k + 1)],
@@ -233,22 +309,31 @@ def learn_qso_model(spectra, z_qsos, k: int = P.K, max_iter: int = 2000, max_fun
                 max_noise_variance=P.MAX_NOISE_VARIANCE,
                 minFunc_output=dict(iterations=res.nit, funcCount=evals, message=str(res.message),
                                     nonfinite_initial_log_omega=int(np.count_nonzero(bad))))
+    if forest is not None:
+        out.update(num_forest_lines=int(forest["num_forest_lines"]),
+                   forest_variance_series=bool(forest["variance_series"]), forest_mean_flux=bool(forest["mean_flux"]),
+                   mean_flux_tau_0=float(forest["mean_flux_tau_0"]), mean_flux_beta=float(forest["mean_flux_beta"]))
+    return out
 
 
 def run_learn_qso_model(base_directory: str, training_release: str, training_set_name: str, train_ind,
-                        k: int = P.K, max_iter: int = 2000, max_fun_evals: int = 4000, device: int = 0) -> dict:
+                        k: int = P.K, max_iter: int = 2000, max_fun_evals: int = 4000, device: int = 0,
+                        forest=None) -> dict:
     """The script on files (learn_qso_model.m:1-131): catalog.mat and preloaded_qsos.mat of
     ``training_release`` in, learned_qso_model_<training_set_name>.mat (v7.3) out.  ``train_ind``
     is the reference's index expression over ``catalog`` (e.g. README.md:148-152), a callable or
-    a boolean array."""
+    a boolean array.  With ``forest`` the file also holds ``process.FOREST_VARIABLES`` as
+    ``process_qsos`` writes them (doubles; the two flags 0 / 1)."""
     from .matv73 import loadmat, savemat73
-    from .process import evaluate_index, load_preloaded_qsos, processed_directory
+    from .process import FOREST_VARIABLES, evaluate_index, load_preloaded_qsos, processed_directory
+    forest = _forest_spec(forest)
     d = processed_directory(base_directory, training_release)
     catalog = loadmat(f"{d}/catalog.mat")
     tind = evaluate_index(train_ind, catalog=catalog).astype(bool).ravel()
     spectra = load_preloaded_qsos(f"{d}/preloaded_qsos.mat", tind)                 # :10-19
     z_qsos = np.asarray(catalog["z_qsos"], dtype=np.float64).ravel()[tind]          # :21
-    out = learn_qso_model(spectra, z_qsos, k=k, max_iter=max_iter, max_fun_evals=max_fun_evals, device=device)
+    out = learn_qso_model(spectra, z_qsos, k=k, max_iter=max_iter, max_fun_evals=max_fun_evals, device=device,
+                          forest=forest)
     save = {key: val for key, val in out.items() if key != "minFunc_output"}
     save["minFunc_output"] = {kk: (vv if isinstance(vv, str) else np.float64(vv))
                               for kk, vv in out["minFunc_output"].items()}
@@ -257,7 +342,7 @@ def run_learn_qso_model(base_directory: str, training_release: str, training_set
     for key in ("rest_wavelengths", "mu", "log_omega", "initial_log_omega"):
         save[key] = np.asarray(save[key], dtype=np.float64).reshape(1, -1)          # MATLAB rows
     for key in ("log_c_0", "log_tau_0", "log_beta", "log_likelihood", "initial_log_c_0",
-                "initial_tau_0", "initial_beta", "max_noise_variance"):
+                "initial_tau_0", "initial_beta", "max_noise_variance") + (FOREST_VARIABLES if forest else ()):
         save[key] = np.float64(save[key])
     savemat73(f"{d}/learned_qso_model_{training_set_name}.mat", save)              # :122-131
     return out

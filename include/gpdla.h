@@ -472,6 +472,29 @@ int gpdla_spectrum_loss_f64(const double* y, const double* lya_1pz, const double
                             double tau_0, double beta, double* nlog_p, double* dM, double* dlog_omega,
                             double* dlog_c_0, double* dlog_tau_0, double* dlog_beta);
 
+/* ---- The Lyman-series forest in the training objective ------------------------
+ * The null model gpdla_engine_set_forest evaluates with variance_series, as the objective: spectrum_loss's
+ * optical depth tau_0 lya_1pz^beta (spectrum_loss.m:23) becomes the series sum above,
+ *   tau = sum_{i=1..L} t_i(tau_0, beta)   at   lambda = lya_1pz lambda_1,   z_QSO the spectrum's own,
+ * by the same device function, comparison and line order; d tau / d log tau_0 = tau and
+ * d tau / d log beta = beta sum_i t_i log(1 + z_i) enter the gradient.  Everything else is objective.m.
+ * gpdla_objective_set_forest copies z_qsos[num_quasars] (host or device memory) and applies to every later
+ * _eval; z_qsos = NULL restores the Lya-only objective.  GPDLA_EINVAL for num_forest_lines outside 1..31,
+ * a bad memory kind or a non-finite z. */
+int gpdla_objective_set_forest(gpdla_objective* objective, const double* z_qsos, int32_t memory,
+                               int32_t num_forest_lines);
+/* gpdla_spectrum_loss_f64 under the series, for one spectrum at z_qso. */
+int gpdla_spectrum_loss_forest_f64(const double* y, const double* lya_1pz, const double* noise_variance,
+                                   const double* M, const double* omega2, int64_t n, int32_t k, double c_0,
+                                   double tau_0, double beta, double z_qso, int32_t num_forest_lines,
+                                   double* nlog_p, double* dM, double* dlog_omega, double* dlog_c_0,
+                                   double* dlog_tau_0, double* dlog_beta);
+/* sum_i t_i(tau_0, beta) for a num_quasars x num_pixels row-major matrix of 1 + z_Lya (host buffers), row q
+ * at z_qsos[q] and lambda = lya_1pz lambda_1: gpdla_forest_f64's sum, one block per row.  NaN in gives NaN
+ * out.  exp(-out) with Kim et al.'s tau_0, beta is the mean flux the training preparation divides out. */
+int gpdla_forest_rows_f64(int32_t device, const double* lya_1pzs, const double* z_qsos, int64_t num_quasars,
+                          int64_t num_pixels, double tau_0, double beta, int32_t num_forest_lines, double* out);
+
 /* ---- DLA parameter samples ------------------------------------------------------
  * generate_dla_samples.m:8-57 on the device: the RR2-scrambled Halton points (:8-9), ksdensity of the
  * catalogue's column densities on the 1,000-point fit grid at MATLAB's default bandwidth (:32-33), the
