@@ -181,6 +181,7 @@ SIGNATURES = {
     "gpdla_posterior_summary_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, dp, i32p,
                                               C.c_int32, C.POINTER(SummarySpec), i32p, dp, dp, dp, dp]),
     "gpdla_engine_set_forest": (C.c_int, [C.c_void_p, C.POINTER(Forest)]),
+    "gpdla_engine_set_forest_scoped": (C.c_int, [C.c_void_p, C.POINTER(Forest), C.c_int32]),
     "gpdla_forest_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, dp]),
     "gpdla_engine_process_models": (C.c_int, [C.c_void_p, C.POINTER(Spectra), C.POINTER(MultiDla), C.POINTER(SubDla),
                                               C.POINTER(ResultsMulti), C.POINTER(ResultsSub), C.POINTER(SummarySpec),

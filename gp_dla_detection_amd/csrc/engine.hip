@@ -98,7 +98,7 @@ struct TimedLaunch {
   hipEvent_t start, stop;
   int kind;  // 0 prep, 1 likelihood, 2 reduce, 3 contraction (panel-GEMM paths, inside 1);
              // gpdla_engine_process_multi only: 4 resample, 5 level >= 2 sweep, 6 its log-mean-exp;
-             // 7 posterior summaries (gpdla_engine_process_summaries); 8 forest kernel; gpdla_engine_process_models
+             // 7 posterior summaries (gpdla_engine_process_summaries); 8 forest kernels; gpdla_engine_process_models
              // only: 9 sub-DLA sweep, 10 its log-mean-exp and MAP launches; 11 population launches
              // (gpdla_engine_process_population)
   int level; // multi-DLA level the span also counts for in gpdla_multi_stats (0: none)
@@ -212,6 +212,7 @@ struct gpdla_engine {
   // Lyman-series forest (gpdla_engine_set_forest): applied by every process* call while set
   bool forest_on = false;
   gpdla_forest forest{};
+  int32_t forest_scope = 0;          // gpdla_engine_set_forest_scoped: 0 mu, 1 mu and M, 2 mu, M and omega^2
   // sub-DLA model (gpdla_engine_process_models): the call's column densities in sweep and in caller
   // order and their log10, a batch's [nq][S] sample rows, [nq] evidences, the sweep's discarded null
   // lane and the MAP outputs ([nq] index / value, [nq][kMaxDlas] pairs)
@@ -971,13 +972,21 @@ int gpdla_engine_process(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_r
       fa.mf_tau_0 = e->forest.mean_flux_tau_0; fa.mf_beta = e->forest.mean_flux_beta;
       fa.num_lines = e->forest.num_forest_lines;
       fa.variance_series = e->forest.variance_series != 0; fa.mean_flux = e->forest.mean_flux != 0;
+      fa.mean_flux_scope = e->forest_scope;
       fa.panel = e->d_panel;
       TimedLaunch t8{};
       if ((rc = record_start(e, &t8, 8))) return rc;
       HIP_TRY(launch_forest(e->K, fa, st));
       HIP_TRY(hipEventRecord(t8.stop, st));
       e->pending.push_back(t8);
-      if (pipe) HIP_TRY(hipEventRecord(hst.in_free, st));  // the forest kernel reads the wavelengths too
+      if (e->forest_scope != 0) {  // the mean flux on the M rows (and omega^2): gpdla_engine_set_forest_scoped
+        TimedLaunch t8c{};
+        if ((rc = record_start(e, &t8c, 8))) return rc;
+        HIP_TRY(launch_forest_covariance(e->K, fa, st));
+        HIP_TRY(hipEventRecord(t8c.stop, st));
+        e->pending.push_back(t8c);
+      }
+      if (pipe) HIP_TRY(hipEventRecord(hst.in_free, st));  // the forest kernels read the wavelengths too
     }
     if ((rc = record_start(e, &t1, 1))) return rc;
     if (batch_i8) {
@@ -1533,13 +1542,20 @@ int gpdla_engine_get_population_stats(gpdla_engine* e, double* ms, int64_t* laun
   return GPDLA_OK;
 }
 
-int gpdla_engine_set_forest(gpdla_engine* e, const gpdla_forest* f) {
+int gpdla_engine_set_forest(gpdla_engine* e, const gpdla_forest* f) { return gpdla_engine_set_forest_scoped(e, f, 0); }
+
+int gpdla_engine_set_forest_scoped(gpdla_engine* e, const gpdla_forest* f, int32_t scope) {
   if (!e) return set_error(GPDLA_EINVAL, "null engine");
+  if (scope < 0 || scope > 2) return set_error(GPDLA_EINVAL, "mean_flux_scope=%d outside [0, 2]", scope);
   if (!f) {
+    if (scope != 0) return set_error(GPDLA_EINVAL, "mean_flux_scope=%d without a forest", scope);
     e->forest_on = false;
     e->forest = gpdla_forest{};
+    e->forest_scope = 0;
     return GPDLA_OK;
   }
+  if (scope != 0 && f->mean_flux == 0)
+    return set_error(GPDLA_EINVAL, "mean_flux_scope=%d needs mean_flux (there is no mean flux to multiply by)", scope);
   if (f->num_forest_lines < 1 || f->num_forest_lines > kMaxLines)
     return set_error(GPDLA_EINVAL, "num_forest_lines=%d outside [1, %d]", f->num_forest_lines, kMaxLines);
   if (!(f->mean_flux_tau_0 >= 0.0 && f->mean_flux_tau_0 < INFINITY))
@@ -1549,6 +1565,7 @@ int gpdla_engine_set_forest(gpdla_engine* e, const gpdla_forest* f) {
     return set_error(GPDLA_EUNSUPPORTED, "the forest needs the fused fp64 path (this engine runs a panel-GEMM or int8 path)");
   e->forest = *f;
   e->forest_on = f->variance_series != 0 || f->mean_flux != 0;
+  e->forest_scope = scope;
   return GPDLA_OK;
 }
 

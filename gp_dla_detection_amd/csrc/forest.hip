@@ -6,6 +6,8 @@
 // between prep_kernel and the likelihood sweep and rewrites the kMu / kOmega2 words of the valid
 // slots of the fused layout; forest_f64_kernel is the same sum on a plain wavelength array.  The sum
 // itself (forest_tables, forest_tau) is forest_series.h's, which the training objective shares.
+// forest_covariance_kernel follows forest_kernel when the mean flux also
+// multiplies the M rows (and omega^2): it rescales the u-words and rebuilds the Khatri-Rao entries.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -62,6 +64,75 @@ __global__ __launch_bounds__(256) void forest_kernel(ForestArgs a) {
   }
 }
 
+// Mean-flux suppression of the covariance: after forest_kernel, the u-words of
+// every valid slot (M_i 2^(E/2), entries 4 kGT + i) are multiplied by the slot's mean flux F, the Gram
+// entries are rebuilt as products of the scaled u-words of their pair (prep_kernel pass 3b's table), and
+// under scope 2 the kOmega2 word is multiplied by F F.  F is forest_kernel's double: forest_tau at the
+// pixel's own wavelength.  Blocks take 256 slots at a time: one thread per slot forms F (no lane repeats
+// a pow) into LDS, then one wave per slot rewrites the row with lanes over entries.  Slots without a
+// pixel, the tile padding, the columns of a padded rank (0 F = 0) and the other spare words are left as
+// prep_kernel wrote them.
+template <int K>
+__global__ __launch_bounds__(256) void forest_covariance_kernel(ForestArgs a) {
+  using Lay = Layout<K>;
+  __shared__ double s_lam[kMaxLines], s_c[kMaxLines];
+  __shared__ double s_F[256];            // the 256 slots' F, or -1: no pixel
+  __shared__ double s_M[4][K];           // each wave's scaled u-words of its current slot
+  __shared__ uint16_t s_rc[Lay::kNGram];
+  forest_tables(s_lam, s_c);
+  const int q = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const SpecInfo inf = a.info[q];
+  if (inf.J == 0) return;
+  for (int e = tid; e < Lay::kNGram; e += 256) {
+    int r, c;
+    gram_pair<K>(e, r, c);
+    s_rc[e] = (uint16_t)(r | (c << 8));
+  }
+  const int64_t pb = a.offsets[q];
+  const double* wl = a.wavelengths + pb;
+  const double z = a.z_qsos[q];
+  const int64_t sb = inf.slot_base, cap = a.slot_cap[q];
+  const int32_t* smap = a.slot_pixel + sb;
+  const int L = inf.L, J = inf.J;
+  const int Ls = L > 0 ? ((L + kChunkSteps - 1) / kChunkSteps) * kChunkSteps : kChunkSteps;
+  double* sM = s_M[wave];
+  for (int64_t j0 = 256 * (int64_t)blockIdx.y; j0 < cap; j0 += 256 * (int64_t)gridDim.y) {
+    __syncthreads();  // s_rc (first round); the previous round's reads of s_F
+    {
+      const int64_t j = j0 + tid;
+      const int gg = (int)(j / Ls), t = (int)(j - (int64_t)gg * Ls);
+      const int pos = (j < cap && gg < 4 && t < L) ? gg * L + t : -1;
+      const int pix = (pos >= 0 && pos < J) ? smap[pos] : -1;
+      s_F[tid] = pix >= 0 ? exp(-forest_tau(wl[pix], z, a.mf_tau_0, a.mf_beta, a.num_lines, s_lam, s_c)) : -1.0;
+    }
+    __syncthreads();
+    for (int i = 0; i < 64; ++i) {
+      const double F = s_F[64 * wave + i];  // wave-uniform
+      if (F < 0.0) continue;
+      double* row = a.panel + (sb + j0 + 64 * wave + i) * Lay::kRow;
+      if (lane < K) {
+        const int e = 4 * Lay::kGT + lane;
+        double* w = row + (e & 3) * Lay::kJS + (e >> 2);
+        const double v = *w * F;  // (M 2^(E/2)) F = (M F) 2^(E/2): one rounding, the definition's
+        *w = v;
+        sM[lane] = v;
+      }
+      if (lane == 63 && a.mean_flux_scope == 2) row[Lay::kOmega2] = row[Lay::kOmega2] * (F * F);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the wave's LDS row before its reads
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (int e = lane; e < Lay::kNGram; e += 64) {
+        const int rc = s_rc[e];
+        row[(e & 3) * Lay::kJS + (e >> 2)] = sM[rc & 255] * sM[rc >> 8];
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // reads of this slot's row done before
+      __builtin_amdgcn_wave_barrier();                         // the next slot overwrites it
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void forest_f64_kernel(const double* __restrict__ wl, int64_t n, double z_qso,
                                                          double tau_0, double beta, int32_t L,
                                                          double* __restrict__ out) {
@@ -84,6 +155,20 @@ hipError_t launch_forest(int K, ForestArgs a, hipStream_t s) {
   if (a.q_count < 1) return hipSuccess;
   hipLaunchKernelGGL(forest_kernel, dim3((unsigned)a.q_count, 4), dim3(256), 0, s, a);
   return hipGetLastError();
+}
+
+hipError_t launch_forest_covariance(int K, const ForestArgs& a, hipStream_t s) {
+  if (a.num_lines < 1 || a.num_lines > kMaxLines || !a.mean_flux || a.mean_flux_scope < 1 || a.mean_flux_scope > 2)
+    return hipErrorInvalidValue;
+  if (a.q_count < 1) return hipSuccess;
+#define X(k)                                                                                                  \
+  if (K == k) {                                                                                               \
+    hipLaunchKernelGGL(forest_covariance_kernel<k>, dim3((unsigned)a.q_count, 4), dim3(256), 0, s, a);        \
+    return hipGetLastError();                                                                                 \
+  }
+  GPDLA_FOR_EACH_RANK(X)
+#undef X
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_forest_f64(const double* wl, int64_t n, double z_qso, double tau_0, double beta, int32_t L,

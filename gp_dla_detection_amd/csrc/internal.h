@@ -604,10 +604,14 @@ struct ForestArgs {
   double mf_tau_0, mf_beta;      // mean flux
   int32_t num_lines;             // L, 1..kMaxLines
   int32_t variance_series, mean_flux;
+  int32_t mean_flux_scope;       // what the mean flux multiplies: 0 mu, 1 mu and M, 2 mu, M and omega^2
   int32_t row, w_mu, w_omega2;   // set by launch_forest: Layout<K>::kRow, kMu, kOmega2
   double* panel;
 };
 hipError_t launch_forest(int K, ForestArgs a, hipStream_t s);
+// the M rows (u-words and Khatri-Rao entries) and, under scope 2, the kOmega2 words of the valid slots
+// times the mean flux; after launch_forest, only with mean_flux and scope 1 or 2
+hipError_t launch_forest_covariance(int K, const ForestArgs& a, hipStream_t s);
 // sum_i t_i(tau_0, beta) at n wavelengths (device buffers), the device function forest_kernel calls
 hipError_t launch_forest_f64(const double* wl, int64_t n, double z_qso, double tau_0, double beta, int32_t L,
                              double* out, hipStream_t s);

@@ -30,6 +30,20 @@ _PATHS = {"auto": L.PATH_AUTO, "fused": L.PATH_FUSED, "panel_gemm": L.PATH_PANEL
           "panel_gemm_i8_24": L.PATH_PANEL_GEMM_I8_24}
 
 
+# what the forest's mean flux multiplies -> the scope code of gpdla_engine_set_forest_scoped
+MEAN_FLUX_SCOPES = {"mu": 0, "mu_M": 1, "all": 2}
+
+
+def mean_flux_scope_code(scope, mean_flux) -> int:
+    """The code of a ``mean_flux_scope`` name; ValueError for an unknown name and for a scope other than
+    "mu" without ``mean_flux`` (there is no mean flux to multiply by)."""
+    if not isinstance(scope, str) or scope not in MEAN_FLUX_SCOPES:
+        raise ValueError(f"mean_flux_scope must be one of {list(MEAN_FLUX_SCOPES)}, not {scope!r}")
+    if scope != "mu" and not mean_flux:
+        raise ValueError(f"mean_flux_scope={scope!r} needs mean_flux=True")
+    return MEAN_FLUX_SCOPES[scope]
+
+
 def _params_struct(p: Parameters, max_batch_spectra: int = 0, path: str = "auto") -> L.Params:
     return L.Params(num_lines=p.num_lines, width=p.width, pixel_spacing=p.pixel_spacing,
                     min_lambda=p.min_lambda, max_lambda=p.max_lambda,
@@ -385,26 +399,31 @@ class Engine:
 
     # --------------------------------------------------------------------- sub-DLA model and forest
     def set_forest(self, forest=None, *, num_forest_lines: int = 31, variance_series: bool = True,
-                   mean_flux: bool = True, mean_flux_tau_0: float = 0.0023, mean_flux_beta: float = 3.65) -> None:
-        """The Lyman-series forest of every later ``process*`` call (gpdla_engine_set_forest).  ``forest`` is
-        None (the Lya-only null model, as before), True (the keyword defaults: 31 lines, both parts, Kim et
-        al. 2007's mean flux) or a dict of those keywords.  ``variance_series``: omega^2 sums the series
-        with the model's tau_0, beta, c_0; ``mean_flux``: mu is multiplied by exp(-sum_i tau_0 c_i (1 + z_i)^beta)
-        for every model.  Fused fp64 path only."""
+                   mean_flux: bool = True, mean_flux_tau_0: float = 0.0023, mean_flux_beta: float = 3.65,
+                   mean_flux_scope: str = "mu") -> None:
+        """The Lyman-series forest of every later ``process*`` call (gpdla_engine_set_forest_scoped).
+        ``forest`` is None (the Lya-only null model, as before), True (the keyword defaults: 31 lines, both
+        parts, Kim et al. 2007's mean flux) or a dict of those keywords.  ``variance_series``: omega^2 sums
+        the series with the model's tau_0, beta, c_0; ``mean_flux``: mu is multiplied by
+        F = exp(-sum_i tau_0 c_i (1 + z_i)^beta) for every model.  ``mean_flux_scope`` says what else F
+        multiplies (``MEAN_FLUX_SCOPES``): "mu" nothing (the default), "mu_M" the rows of M, "all" the rows
+        of M and omega^2 (by F^2) -- the model ``learn_qso_model(forest=dict(mean_flux=True))`` learns;
+        other than "mu" it needs ``mean_flux`` (ValueError).  Fused fp64 path only."""
         if forest is None or forest is False:
             L.check(self.lib.gpdla_engine_set_forest(self._h, None))
             return
         kw = dict(num_forest_lines=num_forest_lines, variance_series=variance_series, mean_flux=mean_flux,
-                  mean_flux_tau_0=mean_flux_tau_0, mean_flux_beta=mean_flux_beta)
+                  mean_flux_tau_0=mean_flux_tau_0, mean_flux_beta=mean_flux_beta, mean_flux_scope=mean_flux_scope)
         if isinstance(forest, dict):
             unknown = set(forest) - set(kw)
             if unknown:
                 raise TypeError(f"unexpected forest settings {sorted(unknown)}")
             kw.update(forest)
+        scope = mean_flux_scope_code(kw["mean_flux_scope"], kw["mean_flux"])
         fs = L.Forest(num_forest_lines=int(kw["num_forest_lines"]), variance_series=int(bool(kw["variance_series"])),
                       mean_flux=int(bool(kw["mean_flux"])), mean_flux_tau_0=float(kw["mean_flux_tau_0"]),
                       mean_flux_beta=float(kw["mean_flux_beta"]))
-        L.check(self.lib.gpdla_engine_set_forest(self._h, C.byref(fs)))
+        L.check(self.lib.gpdla_engine_set_forest_scoped(self._h, C.byref(fs), scope))
 
     def process_models(self, packed: dict, max_dlas: int = 1, sub_dla=None, log_nhi_samples=None, z_edges=None,
                        log_nhi_edges=None, sub_dla_log_nhi=None, want_samples: bool = True, **kwargs) -> dict:

@@ -20,7 +20,7 @@ import os
 import numpy as np
 
 from . import parameters as P
-from .engine import Engine
+from .engine import Engine, mean_flux_scope_code
 from .parameters import Parameters, set_parameters
 from .synthetic import pack_spectra
 
@@ -177,11 +177,13 @@ def _sub_dla_spec(sub_dla, samples: dict, device: int = 0):
 
 
 FOREST_DEFAULTS = dict(num_forest_lines=31, variance_series=True, mean_flux=True, mean_flux_tau_0=0.0023,
-                       mean_flux_beta=3.65)   # Kim et al. 2007's mean flux
+                       mean_flux_beta=3.65,   # Kim et al. 2007's mean flux
+                       mean_flux_scope="mu")  # what the mean flux multiplies (engine.MEAN_FLUX_SCOPES)
 
 
 def _forest_spec(forest):
-    """``forest`` of process_qsos -> None (off) or the full settings dict (True = FOREST_DEFAULTS)."""
+    """``forest`` of process_qsos -> None (off) or the full settings dict (True = FOREST_DEFAULTS).
+    ValueError for an unknown ``mean_flux_scope`` and for one other than "mu" with ``mean_flux=False``."""
     if forest is None or forest is False:
         return None
     given = {} if forest is True else forest
@@ -192,7 +194,14 @@ def _forest_spec(forest):
         raise ValueError("num_forest_lines must be 1..31")
     if not (np.isfinite(f["mean_flux_tau_0"]) and f["mean_flux_tau_0"] >= 0 and np.isfinite(f["mean_flux_beta"])):
         raise ValueError("mean_flux_tau_0 must be finite and >= 0, mean_flux_beta finite")
+    mean_flux_scope_code(f["mean_flux_scope"], f["mean_flux"])
     return f
+
+
+def _scope_variables(forest) -> dict:
+    """MEAN_FLUX_SCOPE_VARIABLES of a run or a learned model: nothing under the default scope."""
+    code = mean_flux_scope_code(forest["mean_flux_scope"], forest["mean_flux"])
+    return dict(mean_flux_scope=float(code)) if code else {}
 
 
 def _select(spectra, test_ind):
@@ -501,7 +510,7 @@ def _finish(res: dict, z_qsos, prior: dict | None, params: Parameters, metadata:
         out = _finish(res, z_qsos, prior, params, metadata, max_dlas, summaries, sub)
         out.update(num_forest_lines=int(forest["num_forest_lines"]), forest_variance_series=bool(forest["variance_series"]),
                    forest_mean_flux=bool(forest["mean_flux"]), mean_flux_tau_0=float(forest["mean_flux_tau_0"]),
-                   mean_flux_beta=float(forest["mean_flux_beta"]))
+                   mean_flux_beta=float(forest["mean_flux_beta"]), **_scope_variables(forest))
         return out
     if _summary_grid(summaries) is not None:
         return _finish_summaries(_finish(res, z_qsos, prior, params, metadata, max_dlas, None, sub), res, summaries, max_dlas)
@@ -561,8 +570,11 @@ def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
     ``log_priors_no_dla`` becomes log(1 - p - r p) and ``p_dlas`` = 1 - p_no_dlas - p_lls.  ``forest`` (True, or
     a dict overriding FOREST_DEFAULTS) makes the null model sum the Lyman series in omega^2
     (``variance_series``) and suppress mu by the mean flux (``mean_flux``), for every model; the output
-    records FOREST_VARIABLES.  Both run on the fused fp64 path only; without them every variable is as
-    before, bit for bit.  A ``compute`` replacement receives ``sub_dla=`` (dict(nhi, log_nhi, ratio)) and
+    records FOREST_VARIABLES.  Its ``mean_flux_scope`` says what the mean flux F multiplies: "mu" (the
+    default) mu alone, "mu_M" also the rows of M (the lineage's inference), "all" also omega^2 (by F^2) --
+    the model ``learn_qso_model(forest=dict(mean_flux=True))`` learns; other than "mu" the output also
+    records MEAN_FLUX_SCOPE_VARIABLES (1 or 2).  Both run on the fused fp64 path only; without them every
+    variable is as before, bit for bit.  A ``compute`` replacement receives ``sub_dla=`` (dict(nhi, log_nhi, ratio)) and
     ``forest=`` (the full settings) when they are set.
 
     ``population`` (``dict(z_edges=..., log_nhi_edges=..., p_thresh_sample=1e-4, p_switch=0.25)``) has the
@@ -619,6 +631,9 @@ SUB_DLA_VARIABLES = ("log_priors_lls", "log_likelihoods_lls", "log_posteriors_ll
 # what a run with the Lyman-series forest records (process_qsos(forest=...))
 FOREST_VARIABLES = ("num_forest_lines", "forest_variance_series", "forest_mean_flux", "mean_flux_tau_0",
                     "mean_flux_beta")
+# ... and, only when forest["mean_flux_scope"] is not "mu", what the mean flux multiplied: 1 mu and M,
+# 2 mu, M and omega^2 (a double; files of the default scope have no such variable)
+MEAN_FLUX_SCOPE_VARIABLES = ("mean_flux_scope",)
 # what a run with the population statistics saves besides (process_qsos(population=...)); catalog.py reads them
 POPULATION_VARIABLES = ("population_poisson", "population_large_inds", "population_large_probs",
                         "population_large_bins", "population_p_dlas", "population_z_edges",
@@ -644,11 +659,12 @@ def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
     has no sample array (and no ``base_sample_inds``) to write.  A run with ``sub_dla`` writes the
     SUB_DLA_VARIABLES (``model_posteriors`` is then Q x (1 + D + 1), the sub-DLA column last, so h5py's
     ``model_posteriors[2]`` still reads "exactly two DLAs", calc_cddf.py:67), one with ``forest`` the
-    FOREST_VARIABLES, one with ``population`` the POPULATION_VARIABLES."""
+    FOREST_VARIABLES (and, with a ``mean_flux_scope`` other than "mu", MEAN_FLUX_SCOPE_VARIABLES), one
+    with ``population`` the POPULATION_VARIABLES."""
     mat = {}
     multi = int(np.ravel(out.get("max_dlas", 1))[0]) > 1
     for key in (PROCESSED_VARIABLES + (MULTI_DLA_VARIABLES if multi else ()) + SUMMARY_VARIABLES + SUB_DLA_VARIABLES +
-                FOREST_VARIABLES + POPULATION_VARIABLES):
+                FOREST_VARIABLES + MEAN_FLUX_SCOPE_VARIABLES + POPULATION_VARIABLES):
         if key not in out:
             continue
         v = out[key]
@@ -855,6 +871,7 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
         raise NotImplementedError("summaries / save_samples=False with world > 1: the summaries are not gathered")
     if sub_dla is not None and sub_dla is not False and world > 1:
         raise NotImplementedError("sub_dla with world > 1: the sub-DLA arrays are not gathered")
+    _forest_spec(forest)    # bad settings (an unknown mean_flux_scope, ...) before any file is opened
     from .matv73 import LazyArray, LazyMat, auto_chunk_rows, is_matv73, loadmat, write_chunks
     from .shard import block_lpt_shards, expected_pixels, merge_shards
     compute = compute or _engine_compute

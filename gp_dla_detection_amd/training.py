@@ -279,7 +279,9 @@ def initial_parameters(centered_rest_fluxes, k: int = P.K):
 def learn_qso_model(spectra, z_qsos, k: int = P.K, max_iter: int = 2000, max_fun_evals: int = 4000,
                     device: int = 0, forest=None) -> dict:
     """learn_qso_model.m:27-131 on preloaded spectra; returns the saved variables, with ``forest`` also
-    ``process.FOREST_VARIABLES`` (the settings the model was trained under)."""
+    ``process.FOREST_VARIABLES`` (the settings the model was trained under) and, when the dict's
+    ``mean_flux_scope`` is not "mu", ``process.MEAN_FLUX_SCOPE_VARIABLES`` (the scope ``process_qsos`` is to
+    evaluate the model under; training is the same for every scope)."""
     from scipy.optimize import minimize
     forest = _forest_spec(forest)
     rest_wavelengths, mu, centered, lya_1pzs, noise = prepare_training_data(spectra, z_qsos, forest=forest,
@@ -313,6 +315,8 @@ def learn_qso_model(spectra, z_qsos, k: int = P.K, max_iter: int = 2000, max_fun
         out.update(num_forest_lines=int(forest["num_forest_lines"]),
                    forest_variance_series=bool(forest["variance_series"]), forest_mean_flux=bool(forest["mean_flux"]),
                    mean_flux_tau_0=float(forest["mean_flux_tau_0"]), mean_flux_beta=float(forest["mean_flux_beta"]))
+        from .process import _scope_variables
+        out.update(_scope_variables(forest))   # recorded only; training itself does not depend on the scope
     return out
 
 
@@ -325,7 +329,8 @@ def run_learn_qso_model(base_directory: str, training_release: str, training_set
     a boolean array.  With ``forest`` the file also holds ``process.FOREST_VARIABLES`` as
     ``process_qsos`` writes them (doubles; the two flags 0 / 1)."""
     from .matv73 import loadmat, savemat73
-    from .process import FOREST_VARIABLES, evaluate_index, load_preloaded_qsos, processed_directory
+    from .process import (FOREST_VARIABLES, MEAN_FLUX_SCOPE_VARIABLES, evaluate_index, load_preloaded_qsos,
+                          processed_directory)
     forest = _forest_spec(forest)
     d = processed_directory(base_directory, training_release)
     catalog = loadmat(f"{d}/catalog.mat")
@@ -342,7 +347,8 @@ def run_learn_qso_model(base_directory: str, training_release: str, training_set
     for key in ("rest_wavelengths", "mu", "log_omega", "initial_log_omega"):
         save[key] = np.asarray(save[key], dtype=np.float64).reshape(1, -1)          # MATLAB rows
     for key in ("log_c_0", "log_tau_0", "log_beta", "log_likelihood", "initial_log_c_0",
-                "initial_tau_0", "initial_beta", "max_noise_variance") + (FOREST_VARIABLES if forest else ()):
+                "initial_tau_0", "initial_beta", "max_noise_variance") + (FOREST_VARIABLES if forest else ()) + tuple(
+                    key for key in MEAN_FLUX_SCOPE_VARIABLES if key in save):
         save[key] = np.float64(save[key])
     savemat73(f"{d}/learned_qso_model_{training_set_name}.mat", save)              # :122-131
     return out

@@ -324,6 +324,17 @@ typedef struct gpdla_forest {
  * GPDLA_EINVAL for L outside 1..31, a non-finite or negative mean_flux_tau_0, a non-finite
  * mean_flux_beta. */
 int gpdla_engine_set_forest(gpdla_engine* engine, const gpdla_forest* forest);
+/* gpdla_engine_set_forest plus what the mean flux F = exp(-sum_i t_i(mean_flux_tau_0, mean_flux_beta))
+ * multiplies, for every model: 0 mu (= gpdla_engine_set_forest, which therefore
+ * also resets a scope set earlier), 1 mu and the rows of M (the Ho, Bird & Garnett 2020 inference), 2 mu,
+ * the rows of M and omega^2 (by F^2, after variance_series): y ~ N(F mu, diag(F) M M' diag(F) +
+ * diag(F^2 omega^2 + sigma^2)), the model training under the mean flux learns.  Each interpolated M entry
+ * is multiplied by F once and the Khatri-Rao entries are products of the scaled entries.  GPDLA_EINVAL
+ * for a scope outside 0..2 and for a scope != 0 with mean_flux == 0 (or forest == NULL);
+ * GPDLA_EUNSUPPORTED on int8 and panel-GEMM engines; a failed call leaves the setting as it was.  Under a
+ * scope != 0 a second kernel follows the forest kernel in every device batch; its time is added to
+ * gpdla_model_stats.forest_ms and it counts in forest_launches (two per batch). */
+int gpdla_engine_set_forest_scoped(gpdla_engine* engine, const gpdla_forest* forest, int32_t mean_flux_scope);
 /* sum_i t_i(tau_0, beta) at n observed wavelengths (host buffers), by the device function the engine's
  * forest kernel calls. */
 int gpdla_forest_f64(int32_t device, const double* wavelengths, int64_t n, double z_qso, double tau_0,

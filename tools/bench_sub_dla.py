@@ -6,7 +6,12 @@ HIP-event accounting: the sub-DLA sweep against the level-1 sweep of the same ca
 against prep_ms of the same call; mean with max - min.  The same calls without the forest are timed in the
 same run (the sweep itself does not depend on it).  Prints one JSON line and, with --out, writes it.
 
-    python tools/bench_sub_dla.py [--spectra 1024] [--samples 10000] [--k 20] [--reps 10] [--out FILE]
+With --scope (mu_M or all) the arms are instead the forest under mean_flux_scope "mu" (the baseline) and
+under that scope, alternated twice within the run.  forest_ms then sums forest_kernel and
+forest_covariance_kernel (two launches per batch); the new launch's time is reported as the difference
+of the arms' forest_ms means, next to prep_ms and the level-1 and sub-DLA sweeps of both arms.
+
+    python tools/bench_sub_dla.py [--spectra 1024] [--samples 10000] [--k 20] [--reps 10] [--scope all] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -37,6 +42,7 @@ def main():
     ap.add_argument("--k", type=int, default=20)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--scope", default=None, choices=("mu_M", "all"))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     Q, S, dev = a.spectra, a.samples, 0
@@ -70,7 +76,13 @@ def main():
             if rc != L.GPDLA_ENUMERIC:
                 L.check(rc)
 
-        for name, forest in (("forest_off", None), ("forest_on", True), ("forest_off_after", None)):
+        arms = (("forest_off", None), ("forest_on", True), ("forest_off_after", None))
+        if a.scope:
+            mu, scoped = dict(mean_flux_scope="mu"), dict(mean_flux_scope=a.scope)
+            arms = (("scope_mu", mu), (f"scope_{a.scope}", scoped), ("scope_mu_again", mu), (f"scope_{a.scope}_again", scoped))
+            rec["scope"] = a.scope
+        for name, forest in arms:
+            launches = 0 if not forest else 2 if forest is not True and forest["mean_flux_scope"] != "mu" else 1
             eng.set_forest(forest)
             for _ in range(a.warmup):
                 call()
@@ -85,7 +97,7 @@ def main():
                 for key in ("sub_dla_ms", "sub_dla_reduce_ms", "forest_ms"):
                     cols[key].append(ms[key])
                 assert st["sample_evals"] == Q * S and ms["sub_dla_launches"] == 1
-                assert ms["forest_launches"] == (1 if forest else 0)
+                assert ms["forest_launches"] == launches
             run = {key: spread(v) for key, v in cols.items()}
             ratios = np.asarray(cols["sub_dla_ms"]) / np.asarray(cols["level1_ms"])
             l1, sd = run["level1_ms"], run["sub_dla_ms"]
@@ -99,6 +111,16 @@ def main():
             run["finite_sub_evidences"] = int(np.isfinite(o_sub.numpy()).sum())
             run["finite_dla_evidences"] = int(np.isfinite(o_dla.numpy()).sum())
             rec["runs"][name] = run
+        if a.scope:
+            runs, sc = rec["runs"], f"scope_{a.scope}"
+            mean2 = lambda arm, key: 0.5 * (runs[arm][key]["mean"] + runs[arm + "_again"][key]["mean"])  # noqa: E731
+            cov = mean2(sc, "forest_ms") - mean2("scope_mu", "forest_ms")
+            rec["covariance_kernel"] = dict(ms=cov, over_prep=cov / mean2("scope_mu", "prep_ms"),
+                                            over_level1=cov / mean2("scope_mu", "level1_ms"))
+            for key in ("level1_ms", "sub_dla_ms"):
+                diff = mean2(sc, key) - mean2("scope_mu", key)
+                sp_ms = max(runs[arm][key]["max_minus_min"] for arm in runs)
+                rec[key + "_scope_minus_mu"] = dict(diff_ms=diff, spread_ms=sp_ms, within_spread=bool(abs(diff) <= sp_ms))
         rec["n_mean"] = float(np.mean(o_n.numpy()))
     line = json.dumps(rec)
     print(line)
