@@ -147,6 +147,11 @@ class Population(C.Structure):
                 ("large_bins", i32p), ("p_dlas", dp)]
 
 
+class LevelPopulation(C.Structure):
+    _fields_ = [("memory", C.c_int32), ("level_posteriors", dp), ("bin_planes", dp), ("poisson_plane", dp),
+                ("large_inds", i32p), ("large_probs", dp), ("large_bins", i32p)]
+
+
 class DlaPrior(C.Structure):
     _fields_ = [("alpha", C.c_double), ("uniform_min", C.c_double), ("uniform_max", C.c_double),
                 ("fit_min", C.c_double), ("fit_max", C.c_double), ("fit_upper", C.c_double)]
@@ -191,6 +196,15 @@ SIGNATURES = {
                                                   C.POINTER(ResultsMulti), C.POINTER(ResultsSub), C.POINTER(SummarySpec),
                                                   C.POINTER(Summaries), C.POINTER(PopulationSpec), C.POINTER(Population)]),
     "gpdla_engine_get_population_stats": (C.c_int, [C.c_void_p, dp, i64p]),
+    "gpdla_engine_process_levels": (C.c_int, [C.c_void_p, C.POINTER(Spectra), C.POINTER(MultiDla), C.POINTER(SubDla),
+                                              C.POINTER(ResultsMulti), C.POINTER(ResultsSub), C.POINTER(SummarySpec),
+                                              C.POINTER(Summaries), C.POINTER(PopulationSpec), C.POINTER(Population),
+                                              C.POINTER(LevelPopulation)]),
+    "gpdla_engine_get_level_population_stats": (C.c_int, [C.c_void_p, dp, i64p]),
+    "gpdla_level_planes_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, dp, i32p,
+                                         C.c_int32, C.POINTER(SummarySpec), dp]),
+    "gpdla_population_split_levels_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, i32p,
+                                                    C.c_int32, dp, C.POINTER(PopulationSpec), dp, i32p, dp, i32p]),
     "gpdla_population_split_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, dp,
                                              C.POINTER(PopulationSpec), dp, i32p, dp, i32p]),
     "gpdla_poisson_binomial_pmf_f64": (C.c_int, [C.c_int32, dp, i64p, C.c_int64, dp]),

@@ -14,7 +14,19 @@ import numpy as np
 PLANE_PI, PLANE_PI2, PLANE_NPI, PLANE_N2PI, PLANE_N2PI2 = range(5)
 
 
-def cddf_moments(bin_planes, p_dlas, keep=None, p_thresh_spec: float = 0.05, moment: bool = False):
+LEVELS = ("first", "all")
+
+
+def _check_levels(levels: str) -> bool:
+    """True for ``levels="all"`` (every absorber of every multi-DLA level), False for "first" (today's
+    level-1 statistics)."""
+    if levels not in LEVELS:
+        raise ValueError(f"levels must be one of {LEVELS}")
+    return levels == "all"
+
+
+def cddf_moments(bin_planes, p_dlas, keep=None, p_thresh_spec: float = 0.05, moment: bool = False,
+                 levels: str = "first", level_posteriors=None):
     """``_get_z_nhi_hist`` (calc_cddf.py:829-870) on the whole (z, log N_HI) grid at once: the expected
     number of DLAs per bin (``moment``: the expected column density) and its variance, the Poisson-binomial
     sum over spectra plus the Poisson sampling term.
@@ -29,7 +41,19 @@ def cddf_moments(bin_planes, p_dlas, keep=None, p_thresh_spec: float = 0.05, mom
 
     which is sum w p pi and sum w^2 (1 - p pi) p pi over a bin's samples (w = 1 or N).  Returns
     (means, variances), each nz x nn; the reference's one-dimensional histograms are their sums over the
-    other axis (dN/dX and Omega_DLA over log N_HI, the CDDF over z)."""
+    other axis (dN/dX and Omega_DLA over log N_HI, the CDDF over z).
+
+    ``levels="all"`` counts every absorber of every level of a multi-DLA run:
+    ``bin_planes`` is then ``bin_planes_levels``, Q x D x 5 x nz x nn (a Q x 5 x nz x nn array counts as D = 1),
+    ``level_posteriors`` the Q x D posteriors P_d of exactly d DLAs (``model_posteriors[:, 1:1 + D]``; for D = 1
+    it defaults to ``p_dlas``), and
+
+        means = sum_q sum_d P_d A_d          variances = sum_q sum_d (P_d B_d - P_d^2 C_d) + means
+
+    with level d's planes, every (level, sample, slot) one Bernoulli trial of probability P_d pi_{d,j}.  The
+    spectrum filter stays ``p_dlas > p_thresh_spec`` and ``keep``."""
+    if _check_levels(levels):
+        return _cddf_moments_levels(bin_planes, p_dlas, keep, p_thresh_spec, moment, level_posteriors)
     planes = np.asarray(bin_planes, dtype=np.float64)
     if planes.ndim != 4 or planes.shape[1] != 5:
         raise ValueError("bin_planes must be Q x 5 x nz x nn")
@@ -45,6 +69,41 @@ def cddf_moments(bin_planes, p_dlas, keep=None, p_thresh_spec: float = 0.05, mom
     for q in np.flatnonzero(use):      # spectrum by spectrum, as the reference accumulates
         means += p[q] * planes[q, a]
         variances += p[q] * planes[q, b] - p[q] * p[q] * planes[q, c]
+    variances += means
+    return means, variances
+
+
+def _cddf_moments_levels(bin_planes, p_dlas, keep, p_thresh_spec, moment, level_posteriors):
+    """``cddf_moments(levels="all")``."""
+    planes = np.asarray(bin_planes, dtype=np.float64)
+    if planes.ndim == 4:
+        planes = planes[:, None]
+    if planes.ndim != 5 or planes.shape[2] != 5:
+        raise ValueError("bin_planes must be Q x D x 5 x nz x nn")
+    Q, D = planes.shape[:2]
+    p = np.asarray(p_dlas, dtype=np.float64).ravel()
+    if p.size != Q:
+        raise ValueError("one p_dla per spectrum")
+    if level_posteriors is None:
+        if D != 1:
+            raise ValueError("levels='all' with D > 1 needs level_posteriors (Q x D)")
+        P = p[:, None]
+    else:
+        P = np.asarray(level_posteriors, dtype=np.float64).reshape(Q, -1)
+        if P.shape[1] != D:
+            raise ValueError("level_posteriors must be Q x D")
+    use = p > p_thresh_spec
+    if keep is not None:
+        use &= np.asarray(keep, dtype=bool).ravel()
+    a, b, c = (PLANE_NPI, PLANE_N2PI, PLANE_N2PI2) if moment else (PLANE_PI, PLANE_PI, PLANE_PI2)
+    means = np.zeros(planes.shape[3:])
+    variances = np.zeros(planes.shape[3:])
+    for q in np.flatnonzero(use):      # spectrum by spectrum, level ascending
+        for d in range(D):
+            if np.isnan(P[q, d]):
+                continue
+            means += P[q, d] * planes[q, d, a]
+            variances += P[q, d] * planes[q, d, b] - P[q, d] * P[q, d] * planes[q, d, c]
     variances += means
     return means, variances
 
@@ -76,18 +135,39 @@ def _population(out):
     return plane, inds, probs, bins, nz, nn
 
 
-def split_distributions(out, keep=None, p_thresh_spec: float = 0.05, axis: str = "log_nhi"):
+def _population_levels(out):
+    """The LEVEL_POPULATION_VARIABLES of the split (``process_qsos(population=dict(..., levels="all"))``) in
+    working form: (Q x D x nz x nn Poisson planes, Q x D x 8 0-based sample indices with -1 = none,
+    probabilities, Q x D x 8 x 4 0-based flat bins, nz, nn)."""
+    plane = np.asarray(out["population_level_poisson"], dtype=np.float64)
+    if plane.ndim != 4:
+        raise ValueError("population_level_poisson must be Q x D x nz x nn")
+    Q, D, nz, nn = plane.shape
+    inds = np.asarray(out["population_level_large_inds"], dtype=np.float64).reshape(Q, D, -1).astype(np.int64) - 1
+    probs = np.asarray(out["population_level_large_probs"], dtype=np.float64).reshape(Q, D, -1)
+    bins = np.asarray(out["population_level_large_bins"], dtype=np.float64).reshape(Q, D, inds.shape[2], -1).astype(np.int64) - 1
+    return plane, inds, probs, bins, nz, nn
+
+
+def split_distributions(out, keep=None, p_thresh_spec: float = 0.05, axis: str = "log_nhi", levels: str = "first"):
     """``_split_distributions_single`` (calc_cddf.py:724-778) from the population variables the engine reduced
     (``process_qsos(population=...)``): per bin of ``axis`` -- ``"log_nhi"`` for the CDDF (the grid collapsed
     over z, ``nhi=True``) or ``"z"`` for dN/dX (collapsed over log N_HI) -- the probabilities kept exactly
     (p >= p_switch; spectrum by spectrum and in sample order within one, the order the reference appends
     them in, :771-773) and the mean of the Poisson approximation to the rest (:767-769,774; summed with
     ``math.fsum`` as there).  Spectra with ``p_dla <= p_thresh_spec`` (:732, ``filter_dla_spectra``) or
-    ``keep`` false contribute nothing.  Returns (list of probability arrays, array of Poisson means)."""
+    ``keep`` false contribute nothing.  Returns (list of probability arrays, array of Poisson means).
+
+    ``levels="all"`` reads the LEVEL_POPULATION_VARIABLES instead: every (level, sample,
+    slot) is one trial of probability P_d pi_{d,j} in the slot's bin, the lists built spectrum by spectrum, level
+    ascending, sample index ascending, slot ascending, and the Poisson mean of a bin the ``fsum`` over every
+    level's plane entries.  The spectrum filter is the same."""
     import math
-    plane, inds, probs, bins, nz, nn = _population(out)
     if axis not in ("log_nhi", "z"):
         raise ValueError("axis must be 'log_nhi' or 'z'")
+    if _check_levels(levels):
+        return _split_distributions_levels(out, keep, p_thresh_spec, axis)
+    plane, inds, probs, bins, nz, nn = _population(out)
     p = np.asarray(out["p_dlas"], dtype=np.float64).ravel()
     if p.size != plane.shape[0]:
         raise ValueError("one p_dla per spectrum")
@@ -104,6 +184,32 @@ def split_distributions(out, keep=None, p_thresh_spec: float = 0.05, axis: str =
         for b in range(nb):
             part = plane[q, :, b] if axis == "log_nhi" else plane[q, b, :]
             small[b].extend(part[part > 0].tolist())
+    return [np.array(v, dtype=np.float64) for v in lists], np.array([math.fsum(v) for v in small])
+
+
+def _split_distributions_levels(out, keep, p_thresh_spec, axis):
+    """``split_distributions(levels="all")``."""
+    import math
+    plane, inds, probs, bins, nz, nn = _population_levels(out)
+    Q, D = plane.shape[:2]
+    p = np.asarray(out["p_dlas"], dtype=np.float64).ravel()
+    if p.size != Q:
+        raise ValueError("one p_dla per spectrum")
+    use = p > p_thresh_spec
+    if keep is not None:
+        use &= np.asarray(keep, dtype=bool).ravel()
+    nb = nn if axis == "log_nhi" else nz
+    lists = [[] for _ in range(nb)]
+    small = [[] for _ in range(nb)]
+    for q in np.flatnonzero(use):
+        for d in range(D):
+            for entry in np.flatnonzero(inds[q, d] >= 0):      # increasing sample index
+                for fb in bins[q, d, entry]:                   # slot ascending
+                    if fb >= 0:
+                        lists[fb % nn if axis == "log_nhi" else fb // nn].append(probs[q, d, entry])
+            for b in range(nb):
+                part = plane[q, d, :, b] if axis == "log_nhi" else plane[q, d, b, :]
+                small[b].extend(part[part > 0].tolist())
     return [np.array(v, dtype=np.float64) for v in lists], np.array([math.fsum(v) for v in small])
 
 
@@ -144,11 +250,13 @@ def count_intervals(pmf, poisson_mean: float):
     return _interval(cdf, 0.0, offset)[0], _interval(cdf, 0.68, offset), _interval(cdf, 0.95, offset)
 
 
-def confidence_intervals(out, keep=None, p_thresh_spec: float = 0.05, axis: str = "log_nhi", device: int = 0, pmf=None):
+def confidence_intervals(out, keep=None, p_thresh_spec: float = 0.05, axis: str = "log_nhi", device: int = 0, pmf=None,
+                         levels: str = "first"):
     """``_get_confidence_intervals`` (calc_cddf.py:800-827): ``split_distributions``, the device pmf of every
     bin's exact list and ``count_intervals``.  ``pmf(lists)`` replaces the device call (tests, as ``compute``
-    does for ``process_qsos``).  Returns (counts [nb], intervals68 [nb x 2], intervals95 [nb x 2])."""
-    lists, means = split_distributions(out, keep, p_thresh_spec, axis)
+    does for ``process_qsos``).  ``levels`` as in ``split_distributions``.  Returns (counts [nb], intervals68
+    [nb x 2], intervals95 [nb x 2])."""
+    lists, means = split_distributions(out, keep, p_thresh_spec, axis, levels)
     pmfs = poisson_binomial_pmf(lists, device=device) if pmf is None else pmf(lists)
     got = [count_intervals(one, mean) for one, mean in zip(pmfs, means)]
     return (np.array([g[0] for g in got]), np.array([g[1] for g in got]).reshape(-1, 2),
@@ -182,13 +290,14 @@ def path_length(z_lo: float, z_hi: float, min_z_dlas, max_z_dlas, keep=None, ome
 
 
 def column_density_function(out, keep=None, p_thresh_spec: float = 0.05, omega_m: float = 0.279, device: int = 0,
-                            pmf=None):
+                            pmf=None, levels: str = "first"):
     """f(N) = n_DLA / dN / dX (calc_cddf.py:440-464) on the population grid of ``out``: the log N_HI bins are
-    ``population_log_nhi_edges`` and the redshift range its whole z extent.  Returns (bin centres in log N_HI,
+    ``population_log_nhi_edges`` and the redshift range its whole z extent; ``levels="all"`` counts every
+    absorber of every multi-DLA level (``split_distributions``).  Returns (bin centres in log N_HI,
     f(N), its 68 % band [nn x 2], its 95 % band, (lower, upper) bin half-widths in N_HI)."""
     ez = np.asarray(out["population_z_edges"], dtype=np.float64).ravel()
     en = np.asarray(out["population_log_nhi_edges"], dtype=np.float64).ravel()
-    n, l68, l95 = confidence_intervals(out, keep, p_thresh_spec, "log_nhi", device, pmf)
+    n, l68, l95 = confidence_intervals(out, keep, p_thresh_spec, "log_nhi", device, pmf, levels)
     dX = path_length(ez[0], ez[-1], out["min_z_dlas"], out["max_z_dlas"], keep, omega_m)
     dN = 10.0 ** en[1:] - 10.0 ** en[:-1]
     cent = (en[1:] + en[:-1]) / 2.0
@@ -196,12 +305,14 @@ def column_density_function(out, keep=None, p_thresh_spec: float = 0.05, omega_m
     return cent, n / dX / dN, l68 / dX / dN[:, None], l95 / dX / dN[:, None], xerrs
 
 
-def line_density(out, keep=None, p_thresh_spec: float = 0.05, omega_m: float = 0.279, device: int = 0, pmf=None):
+def line_density(out, keep=None, p_thresh_spec: float = 0.05, omega_m: float = 0.279, device: int = 0, pmf=None,
+                 levels: str = "first"):
     """dN/dX per redshift bin (calc_cddf.py:490-507) on the population grid of ``out``: the bins are
     ``population_z_edges`` and the column densities its whole log N_HI extent; bins without path are dropped
-    (:500).  Returns (bin centres, dN/dX, 68 % band, 95 % band, (lower, upper) half-widths)."""
+    (:500); ``levels`` as in ``column_density_function``.  Returns (bin centres, dN/dX, 68 % band, 95 % band,
+    (lower, upper) half-widths)."""
     ez = np.asarray(out["population_z_edges"], dtype=np.float64).ravel()
-    n, l68, l95 = confidence_intervals(out, keep, p_thresh_spec, "z", device, pmf)
+    n, l68, l95 = confidence_intervals(out, keep, p_thresh_spec, "z", device, pmf, levels)
     dX = np.array([path_length(a, b, out["min_z_dlas"], out["max_z_dlas"], keep, omega_m) for a, b in zip(ez[:-1], ez[1:])])
     ii = dX > 0
     cent = (ez[1:] + ez[:-1]) / 2.0
@@ -221,14 +332,22 @@ def rho_crit(hubble: float = 0.7) -> float:
     return 3.0 * (H100_PER_S * hubble) ** 2 / (8.0 * math.pi * GRAVITY_CGS)
 
 
-def omega_dla(out, keep=None, p_thresh_spec: float = 0.05, hubble: float = 0.7, omega_m: float = 0.279):
+def omega_dla(out, keep=None, p_thresh_spec: float = 0.05, hubble: float = 0.7, omega_m: float = 0.279,
+              levels: str = "first"):
     """Omega_DLA per redshift bin by summing column densities (calc_cddf.py:638-662), the moment version:
     ``cddf_moments(moment=True)`` on the summary grid of ``out`` (``bin_planes`` with ``bin_z_edges``; every
     log N_HI bin of it counts) over the path lengths, in the reference's units -- m_p H_0 / (c rho_crit), with
     rho_crit at the reference's default h = 0.7 whatever ``hubble`` is (:658 calls it without the argument).
-    Returns (bin centres, Omega_DLA, its standard deviation, the z edges)."""
+    ``levels="all"`` sums ``bin_planes_levels`` with the level posteriors ``model_posteriors[:, 1:1 + D]``
+    (``cddf_moments``).  Returns (bin centres, Omega_DLA, its standard deviation, the z edges)."""
     ez = np.asarray(out["bin_z_edges"], dtype=np.float64).ravel()
-    means, variances = cddf_moments(out["bin_planes"], out["p_dlas"], keep, p_thresh_spec, moment=True)
+    if _check_levels(levels):
+        planes = np.asarray(out["bin_planes_levels"], dtype=np.float64)
+        post = np.asarray(out["model_posteriors"], dtype=np.float64)
+        means, variances = cddf_moments(planes, out["p_dlas"], keep, p_thresh_spec, moment=True, levels="all",
+                                        level_posteriors=post.reshape(planes.shape[0], -1)[:, 1:1 + planes.shape[1]])
+    else:
+        means, variances = cddf_moments(out["bin_planes"], out["p_dlas"], keep, p_thresh_spec, moment=True)
     mean, variance = means.sum(axis=1), variances.sum(axis=1)
     dX = np.array([path_length(a, b, out["min_z_dlas"], out["max_z_dlas"], keep, omega_m) for a, b in zip(ez[:-1], ez[1:])])
     with np.errstate(divide="ignore", invalid="ignore"):

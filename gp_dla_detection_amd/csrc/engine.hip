@@ -100,7 +100,7 @@ struct TimedLaunch {
              // gpdla_engine_process_multi only: 4 resample, 5 level >= 2 sweep, 6 its log-mean-exp;
              // 7 posterior summaries (gpdla_engine_process_summaries); 8 forest kernels; gpdla_engine_process_models
              // only: 9 sub-DLA sweep, 10 its log-mean-exp and MAP launches; 11 population launches
-             // (gpdla_engine_process_population)
+             // (gpdla_engine_process_population); 12 level-population launches (gpdla_engine_process_levels)
   int level; // multi-DLA level the span also counts for in gpdla_multi_stats (0: none)
 };
 
@@ -235,6 +235,15 @@ struct gpdla_engine {
   double population_ms = 0.0;
   int64_t population_launches = 0;
 
+  // population statistics over every level (gpdla_engine_process_levels): a batch's outputs ([D][nq] level
+  // posteriors, [nq][D][5][bins] planes, [nq][D][bins] Poisson planes, [nq][D][8] large samples with
+  // [kMaxDlas] bins each)
+  double *d_lv_post = nullptr, *d_lv_planes = nullptr, *d_lv_plane = nullptr, *d_lv_lprob = nullptr;
+  int32_t *d_lv_lind = nullptr, *d_lv_lbin = nullptr;
+  size_t cap_lv_post = 0, cap_lv_planes = 0, cap_lv_plane = 0, cap_lv_lprob = 0, cap_lv_lind = 0, cap_lv_lbin = 0;
+  double level_population_ms = 0.0;
+  int64_t level_population_launches = 0;
+
   std::vector<TimedLaunch> pending;
   gpdla_stats stats{};
 };
@@ -265,6 +274,7 @@ int resolve_events(gpdla_engine* e) {
     if (t.kind == 9) { e->model_stats.sub_dla_ms += ms; e->model_stats.sub_dla_launches++; }
     if (t.kind == 10) { e->model_stats.sub_dla_reduce_ms += ms; e->model_stats.sub_dla_reduce_launches++; }
     if (t.kind == 11) { e->population_ms += ms; e->population_launches++; }
+    if (t.kind == 12) { e->level_population_ms += ms; e->level_population_launches++; }
     if (t.level >= 1 && t.level <= GPDLA_MAX_DLAS) {
       e->mstats.level_ms[t.level - 1] += ms;
       e->mstats.level_launches[t.level - 1]++;
@@ -371,7 +381,8 @@ void gpdla_engine_destroy(gpdla_engine* e) {
                   e->d_s_ll, e->d_s_z, e->d_s_n, e->d_s_planes, e->d_s_ind, e->d_sub_nhi, e->d_sub_nhi_c,
                   e->d_sub_lognhi, e->d_sub_sll, e->d_sub_ev, e->d_sub_null, e->d_sub_mll, e->d_sub_mz,
                   e->d_sub_mn, e->d_sub_mind, e->d_p_lpno, e->d_p_lpdla, e->d_p_lplls, e->d_p_lognhi, e->d_p_edges,
-                  e->d_p_pdla, e->d_p_plane, e->d_p_lprob, e->d_p_lind, e->d_p_lbin};
+                  e->d_p_pdla, e->d_p_plane, e->d_p_lprob, e->d_p_lind, e->d_p_lbin,
+                  e->d_lv_post, e->d_lv_planes, e->d_lv_plane, e->d_lv_lprob, e->d_lv_lind, e->d_lv_lbin};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (e->h_meta) (void)hipHostFree(e->h_meta);
@@ -1080,6 +1091,8 @@ int gpdla_engine_reset_stats(gpdla_engine* e) {
   e->summary_launches = 0;
   e->population_ms = 0.0;
   e->population_launches = 0;
+  e->level_population_ms = 0.0;
+  e->level_population_launches = 0;
   e->model_stats = gpdla_model_stats{};
   return GPDLA_OK;
 }
@@ -1149,12 +1162,28 @@ static int validate_summary_grid(const gpdla_summary_spec* spec) {
 // level-1 likelihood launch again with the sub-DLA column densities, into workspaces of its own.
 // With pspec / pop (gpdla_engine_process_population) the posterior and split launches of population.hip
 // run per batch after the last level, on the batch's evidences and level-1 rows.
+// With lv (gpdla_engine_process_levels) the launches of level_population.hip follow them, on every level's
+// rows and base indices: the planes when spec has a grid, the posteriors and the split when pspec is given.
 static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
                               const gpdla_results_multi* res, const gpdla_summary_spec* spec,
                               const gpdla_summaries* sums, const gpdla_sub_dla* sub = nullptr,
                               const gpdla_results_sub* rsub = nullptr, const gpdla_population_spec* pspec = nullptr,
-                              const gpdla_population* pop = nullptr) {
+                              const gpdla_population* pop = nullptr, const gpdla_level_population* lv = nullptr) {
   if (!e || !sp || !mu || !res) return set_error(GPDLA_EINVAL, "null argument");
+  // a half is asked for by its arrays: the planes by bin_planes, the posteriors and the split by the rest
+  const bool lv_planes = lv && lv->bin_planes;
+  const bool lv_split = lv && (lv->level_posteriors || lv->poisson_plane || lv->large_inds || lv->large_probs || lv->large_bins);
+  if (lv) {
+    if (!lv_planes && !lv_split) return set_error(GPDLA_EINVAL, "level population without an output array");
+    if (lv->memory != GPDLA_MEM_HOST && lv->memory != GPDLA_MEM_DEVICE)
+      return set_error(GPDLA_EINVAL, "level population memory=%d", lv->memory);
+    if (lv_planes && !(spec && spec->num_z_bins > 0)) return set_error(GPDLA_EINVAL, "level bin_planes need a summary grid");
+    if (lv_split && !pspec) return set_error(GPDLA_EINVAL, "the level population arrays need a population spec");
+    if (lv_split && (!lv->level_posteriors || !lv->poisson_plane || !lv->large_inds || !lv->large_probs || !lv->large_bins))
+      return set_error(GPDLA_EINVAL, "null level population array");
+    if (e->gemm || e->i8)
+      return set_error(GPDLA_EUNSUPPORTED, "the level population needs the fused fp64 path (this engine runs a panel-GEMM or int8 path)");
+  }
   if (pspec) {
     if (!pop) return set_error(GPDLA_EINVAL, "null argument");
     int rcp = validate_population_grid(pspec->num_z_bins, pspec->num_nhi_bins, pspec->z_edges, pspec->log_nhi_edges,
@@ -1476,6 +1505,61 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
       HIP_TRY(hipMemcpyAsync(pop->large_bins + (size_t)q0 * NL, e->d_p_lbin, (size_t)nq * NL * 4, pk, st));
     }
 
+    if (lv) {
+      const size_t NL = kPopulationMaxLarge, Ds = (size_t)D;
+      LevelRowsArgs lr{};
+      lr.rows = (int32_t)nq; lr.levels = D; lr.ll = e->d_m_sll; lr.ld = S; lr.S = S;
+      lr.base = D > 1 ? e->d_m_base : nullptr; lr.ld_base = S;
+      lr.offset = e->d_off_c; lr.zmin = e->d_m_zmin; lr.zmax = e->d_m_zmax;
+      if (lv_planes && (rc = grow(&e->d_lv_planes, &e->cap_lv_planes, (size_t)nq * Ds * kSummaryPlanes * nbins))) return rc;
+      if (lv_split) {
+        if ((rc = grow(&e->d_lv_post, &e->cap_lv_post, (size_t)nq * Ds))) return rc;
+        if ((rc = grow(&e->d_lv_plane, &e->cap_lv_plane, (size_t)nq * Ds * pbins))) return rc;
+        if ((rc = grow(&e->d_lv_lind, &e->cap_lv_lind, (size_t)nq * Ds * NL))) return rc;
+        if ((rc = grow(&e->d_lv_lprob, &e->cap_lv_lprob, (size_t)nq * Ds * NL))) return rc;
+        if ((rc = grow(&e->d_lv_lbin, &e->cap_lv_lbin, (size_t)nq * Ds * NL * kMaxDlas))) return rc;
+      }
+      TimedLaunch t12{};
+      if ((rc = record_start(e, &t12, 12))) return rc;
+      if (lv_planes) {
+        LevelPlanesArgs la{};
+        la.r = lr; la.r.log_nhi = e->d_s_lognhi; la.r.nz = nzb; la.r.nn = nnb;
+        la.r.z_edges = e->d_s_edges; la.r.n_edges = e->d_s_edges + nzb + 1;
+        la.nhi = e->d_nhi_c; la.planes = e->d_lv_planes;
+        HIP_TRY(launch_level_planes(la, st));
+      }
+      if (lv_split) {
+        LevelPosteriorArgs ma{};
+        ma.rows = (int32_t)nq; ma.levels = D; ma.ll_null = e->d_m_null; ma.ll_dla = e->d_m_lldla;
+        ma.ll_lls = sub ? e->d_sub_ev : nullptr;
+        ma.lp_no = e->d_p_lpno + q0; ma.lp_dla = e->d_p_lpdla + q0; ma.lp_lls = sub ? e->d_p_lplls + q0 : nullptr;
+        ma.ld_prior = Q; ma.level_post = e->d_lv_post;
+        LevelSplitArgs la{};
+        la.r = lr; la.r.log_nhi = e->d_p_lognhi; la.r.nz = pnz; la.r.nn = pnn;
+        la.r.z_edges = e->d_p_edges; la.r.n_edges = e->d_p_edges + pnz + 1;
+        la.level_post = e->d_lv_post; la.ld_post = nq;
+        la.p_thresh_sample = pspec->p_thresh_sample; la.p_switch = pspec->p_switch;
+        la.poisson = e->d_lv_plane; la.large_inds = e->d_lv_lind; la.large_probs = e->d_lv_lprob; la.large_bins = e->d_lv_lbin;
+        HIP_TRY(launch_level_posterior(ma, st));
+        HIP_TRY(launch_level_split(la, st));
+      }
+      HIP_TRY(hipEventRecord(t12.stop, st));
+      e->pending.push_back(t12);
+      const hipMemcpyKind lk = lv->memory == GPDLA_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+      if (lv_planes)
+        HIP_TRY(hipMemcpyAsync(lv->bin_planes + (size_t)q0 * Ds * kSummaryPlanes * nbins, e->d_lv_planes,
+                               (size_t)nq * Ds * kSummaryPlanes * nbins * 8, lk, st));
+      if (lv_split) {
+        for (int d = 0; d < D; ++d)
+          HIP_TRY(hipMemcpyAsync(lv->level_posteriors + (int64_t)d * Q + q0, e->d_lv_post + (size_t)d * nq, nq * 8, lk, st));
+        HIP_TRY(hipMemcpyAsync(lv->poisson_plane + (size_t)q0 * Ds * pbins, e->d_lv_plane, (size_t)nq * Ds * pbins * 8, lk, st));
+        HIP_TRY(hipMemcpyAsync(lv->large_inds + (size_t)q0 * Ds * NL, e->d_lv_lind, (size_t)nq * Ds * NL * 4, lk, st));
+        HIP_TRY(hipMemcpyAsync(lv->large_probs + (size_t)q0 * Ds * NL, e->d_lv_lprob, (size_t)nq * Ds * NL * 8, lk, st));
+        HIP_TRY(hipMemcpyAsync(lv->large_bins + (size_t)q0 * Ds * NL * kMaxDlas, e->d_lv_lbin,
+                               (size_t)nq * Ds * NL * kMaxDlas * 4, lk, st));
+      }
+    }
+
     HIP_TRY(hipMemcpyAsync(res->log_likelihoods_no_dla + q0, e->d_m_null, nq * 8, out_kind, st));
     if (res->min_z_dlas) HIP_TRY(hipMemcpyAsync(res->min_z_dlas + q0, e->d_m_zmin, nq * 8, out_kind, st));
     if (res->max_z_dlas) HIP_TRY(hipMemcpyAsync(res->max_z_dlas + q0, e->d_m_zmax, nq * 8, out_kind, st));
@@ -1529,6 +1613,28 @@ int gpdla_engine_process_population(gpdla_engine* e, const gpdla_spectra* sp, co
   if (sub && !rsub) return set_error(GPDLA_EINVAL, "null sub-DLA results");
   if ((pspec == nullptr) != (pop == nullptr)) return set_error(GPDLA_EINVAL, "population spec and outputs go together");
   return process_multi_impl(e, sp, mu, res, spec, spec ? sums : nullptr, sub, sub ? rsub : nullptr, pspec, pop);
+}
+
+int gpdla_engine_process_levels(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
+                                const gpdla_sub_dla* sub, const gpdla_results_multi* res,
+                                const gpdla_results_sub* rsub, const gpdla_summary_spec* spec,
+                                const gpdla_summaries* sums, const gpdla_population_spec* pspec,
+                                const gpdla_population* pop, const gpdla_level_population* lv) {
+  if (spec && !sums) return set_error(GPDLA_EINVAL, "null argument");
+  if (sub && !rsub) return set_error(GPDLA_EINVAL, "null sub-DLA results");
+  if ((pspec == nullptr) != (pop == nullptr)) return set_error(GPDLA_EINVAL, "population spec and outputs go together");
+  return process_multi_impl(e, sp, mu, res, spec, spec ? sums : nullptr, sub, sub ? rsub : nullptr, pspec, pop, lv);
+}
+
+int gpdla_engine_get_level_population_stats(gpdla_engine* e, double* ms, int64_t* launches) {
+  if (!e || !ms || !launches) return set_error(GPDLA_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  int rc = resolve_events(e);
+  if (rc) return rc;
+  *ms = e->level_population_ms;
+  *launches = e->level_population_launches;
+  return GPDLA_OK;
 }
 
 int gpdla_engine_get_population_stats(gpdla_engine* e, double* ms, int64_t* launches) {

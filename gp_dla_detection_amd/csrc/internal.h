@@ -587,6 +587,53 @@ hipError_t launch_population_split(const PopulationSplitArgs& a, hipStream_t s);
 int validate_population_grid(int64_t nz, int64_t nn, const double* z_edges, const double* n_edges,
                              double p_thresh_sample, double p_switch);
 
+// ---- population statistics over every level (level_population.hip): the posterior of each DLA level,
+// and per (row, level) the binned masses and the split of P_d pi_{d,j} with every absorber of a sample's
+// base chain counted (include/gpdla.h "Population statistics over every multi-DLA level")
+struct LevelPosteriorArgs {
+  int32_t rows, levels;
+  const double* ll_null;         // [rows]
+  const double* ll_dla;          // [levels][rows]
+  const double* ll_lls;          // [rows], or nullptr: no sub-DLA model
+  const double* lp_no;           // [rows] log priors
+  const double* lp_dla;          // [levels][ld_prior]
+  const double* lp_lls;          // [rows] with ll_lls
+  int64_t ld_prior;
+  double* level_post;            // [levels][rows]
+};
+struct LevelRowsArgs {           // what both level kernels read
+  int32_t rows, levels;
+  const double* ll;              // [levels][rows][ld], caller's sample order
+  int64_t ld, S;
+  const int32_t* base;           // [levels - 1][rows][ld_base] base indices, or nullptr (levels = 1)
+  int64_t ld_base;
+  const double* offset;          // [S] caller order
+  const double* log_nhi;         // [S]
+  const double* zmin;            // [rows]
+  const double* zmax;            // [rows]
+  int32_t nz, nn;
+  const double* z_edges;         // device [nz + 1]
+  const double* n_edges;         // device [nn + 1]
+};
+struct LevelPlanesArgs {
+  LevelRowsArgs r;
+  const double* nhi;             // [S]
+  double* planes;                // [rows][levels][kSummaryPlanes][nz nn]
+};
+struct LevelSplitArgs {
+  LevelRowsArgs r;
+  const double* level_post;      // [levels][ld_post]
+  int64_t ld_post;
+  double p_thresh_sample, p_switch;
+  double* poisson;               // [rows][levels][nz nn]
+  int32_t* large_inds;           // [rows][levels][kPopulationMaxLarge], -1 = unused
+  double* large_probs;           // NaN = unused
+  int32_t* large_bins;           // [rows][levels][kPopulationMaxLarge][kMaxDlas], -1 = unused
+};
+hipError_t launch_level_posterior(const LevelPosteriorArgs& a, hipStream_t s);
+hipError_t launch_level_planes(const LevelPlanesArgs& a, hipStream_t s);
+hipError_t launch_level_split(const LevelSplitArgs& a, hipStream_t s);
+
 // ---- Lyman-series forest (forest.hip): rewrites the kMu / kOmega2 words of a batch's valid slots
 // between prep_kernel and the sweeps (fused fp64 layout only)
 struct ForestArgs {

@@ -204,12 +204,14 @@ class Engine:
         return dict(summary_ms=ms.value, summary_launches=n.value)
 
     def _run_multi(self, packed, max_dlas, resample_uniforms, base_sample_inds, want_samples, min_z_separation,
-                   occam_log_penalty, raise_numeric, memory, summary, sub=None, models=False, population=None) -> dict:
+                   occam_log_penalty, raise_numeric, memory, summary, sub=None, models=False, population=None,
+                   levels=None) -> dict:
         """process_multi / process_summaries / process_models / process_population: ``summary`` is None or
         the samples' log N_HI and the grid; ``sub`` None or the sub-DLA column densities (``nhi``) and, for the
         MAP outputs, their log10 (``log_nhi``); ``models`` routes the call through gpdla_engine_process_models,
         ``models="population"`` through gpdla_engine_process_population with ``population`` None (both structs
-        NULL) or the normalised dict of ``process_population``."""
+        NULL) or the normalised dict of ``process_population``; ``levels`` (with ``models="population"``) routes
+        it through gpdla_engine_process_levels with the halves it names ("planes", "split")."""
         D, S = int(max_dlas), self.num_samples
         offsets = np.ascontiguousarray(packed["offsets"], dtype=np.int64)
         Q = offsets.size - 1
@@ -285,6 +287,31 @@ class Engine:
                         population_large_bins=np.full((Q, L.POPULATION_MAX_LARGE), -1, dtype=np.int32),
                         population_p_dlas=np.full(Q, np.nan))
 
+        lvout = {}
+        if levels:
+            if "planes" in levels:
+                if spec is None or "bin_planes" not in sout:
+                    raise ValueError("the level planes need a summary grid")
+                lvout["bin_planes_levels"] = np.zeros((Q, Dc) + sout["bin_planes"].shape[1:])
+            if "split" in levels:
+                if pspec is None:
+                    raise ValueError("the level split needs population")
+                NL = L.POPULATION_MAX_LARGE
+                lvout.update(population_level_posteriors=np.full((Dc, Q), np.nan),
+                             population_level_poisson=np.zeros((Q, Dc) + pout["population_poisson"].shape[1:]),
+                             population_level_large_inds=np.full((Q, Dc, NL), -1, dtype=np.int32),
+                             population_level_large_probs=np.full((Q, Dc, NL), np.nan),
+                             population_level_large_bins=np.full((Q, Dc, NL, L.MAX_DLAS), -1, dtype=np.int32))
+
+        def results_levels(mem, get):
+            if not lvout:
+                return None
+            return L.LevelPopulation(memory=mem, level_posteriors=get("population_level_posteriors"),
+                                     bin_planes=get("bin_planes_levels"), poisson_plane=get("population_level_poisson"),
+                                     large_inds=get("population_level_large_inds", C.c_int32),
+                                     large_probs=get("population_level_large_probs"),
+                                     large_bins=get("population_level_large_bins", C.c_int32))
+
         def results_pop(mem, get):
             if pspec is None:
                 return None
@@ -303,7 +330,13 @@ class Engine:
                                 map_log_likelihoods=get("map_log_likelihood_lls"), map_z_lls=get("MAP_z_lls"),
                                 map_log_nhi_lls=get("MAP_log_nhi_lls"))
 
-        def call(sp, rs, sm, rsub=None, rpop=None):
+        def call(sp, rs, sm, rsub=None, rpop=None, rlv=None):
+            if levels is not None:
+                return self.lib.gpdla_engine_process_levels(
+                    self._h, C.byref(sp), C.byref(md), C.byref(subs) if subs is not None else None, C.byref(rs),
+                    C.byref(rsub) if rsub is not None else None, C.byref(spec) if spec is not None else None,
+                    C.byref(sm) if sm is not None else None, C.byref(pspec) if pspec is not None else None,
+                    C.byref(rpop) if rpop is not None else None, C.byref(rlv) if rlv is not None else None)
             if models == "population":
                 return self.lib.gpdla_engine_process_population(
                     self._h, C.byref(sp), C.byref(md), C.byref(subs) if subs is not None else None, C.byref(rs),
@@ -338,7 +371,8 @@ class Engine:
                                  map_z_dlas=L.ptr(sout["map_z_dlas"]), map_log_nhis=L.ptr(sout["map_log_nhis"]),
                                  bin_planes=L.ptr(pl) if pl is not None and pl.size else None)
             rc = call(sp, rs, sm, results_sub(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(subout.get(k), t)),
-                      results_pop(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(pout[k], t) if pout[k].size else None))
+                      results_pop(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(pout[k], t) if pout[k].size else None),
+                      results_levels(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(lvout[k], t) if k in lvout and lvout[k].size else None))
         elif memory == "device":
             dev = {k: L.DeviceArray.from_numpy(v, self.device) for k, v in
                    dict(wl=wl, fl=fl, nv=nv, mk=mk, zq=zq).items()}
@@ -368,9 +402,13 @@ class Engine:
                                  map_log_nhis=sptr("map_log_nhis"), bin_planes=sptr("bin_planes"))
             dsub = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in subout.items() if v.size}
             dpop = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in pout.items() if v.size}
+            dlv = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in lvout.items() if v.size}
             rc = call(sp, rs, sm, results_sub(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dsub[k].ptr, t) if k in dsub else None),
-                      results_pop(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dpop[k].ptr, t) if k in dpop else None))
+                      results_pop(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dpop[k].ptr, t) if k in dpop else None),
+                      results_levels(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dlv[k].ptr, t) if k in dlv else None))
             if rc in (L.GPDLA_OK, L.GPDLA_ENUMERIC):
+                for k, d in dlv.items():
+                    lvout[k] = d.numpy()
                 for k, d in dpop.items():
                     pout[k] = d.numpy()
                 for k, d in dout.items():
@@ -379,7 +417,7 @@ class Engine:
                     sout[k] = d.numpy()
                 for k, d in dsub.items():
                     subout[k] = d.numpy()
-            for d in list(dev.values()) + list(dout.values()) + list(dsum.values()) + list(dsub.values()) + list(dpop.values()):
+            for d in list(dev.values()) + list(dout.values()) + list(dsum.values()) + list(dsub.values()) + list(dpop.values()) + list(dlv.values()):
                 d.free()
         else:
             raise ValueError("memory must be 'host' or 'device'")
@@ -395,6 +433,7 @@ class Engine:
                 out["bin_planes"] = sout["bin_planes"]
         out.update(subout)
         out.update(pout)
+        out.update(lvout)
         return out
 
     # --------------------------------------------------------------------- sub-DLA model and forest
@@ -439,9 +478,9 @@ class Engine:
                                     want_samples, True, None, kwargs)
 
     def _process_models(self, packed, max_dlas, sub_dla, log_nhi_samples, z_edges, log_nhi_edges, sub_dla_log_nhi,
-                        want_samples, entry, population, kwargs) -> dict:
-        """``process_models`` / ``process_population``: ``entry`` and ``population`` are ``_run_multi``'s
-        ``models`` and ``population``."""
+                        want_samples, entry, population, kwargs, levels=None) -> dict:
+        """``process_models`` / ``process_population`` / ``process_levels``: ``entry``, ``population`` and
+        ``levels`` are ``_run_multi``'s ``models``, ``population`` and ``levels``."""
         if (z_edges is None) != (log_nhi_edges is None):
             raise ValueError("z_edges and log_nhi_edges go together")
         if z_edges is not None and log_nhi_samples is None:
@@ -473,7 +512,7 @@ class Engine:
         return self._run_multi(packed, max_dlas, kwargs.get("resample_uniforms"), kwargs.get("base_sample_inds"),
                                want_samples, kwargs.get("min_z_separation"), kwargs.get("occam_log_penalty"),
                                kwargs.get("raise_numeric", False), kwargs.get("memory", "host"), summary, sub, entry,
-                               population)
+                               population, levels)
 
     def process_population(self, packed: dict, max_dlas: int = 1, population=None, sub_dla=None, log_nhi_samples=None,
                            z_edges=None, log_nhi_edges=None, sub_dla_log_nhi=None, want_samples: bool = True,
@@ -492,6 +531,11 @@ class Engine:
                                                  slots -1 / NaN / -1
         ``population=None`` is ``process_models``, bit for bit.  Repeated calls and any ``max_batch_spectra``
         give bitwise equal outputs."""
+        return self._process_models(packed, max_dlas, sub_dla, log_nhi_samples, z_edges, log_nhi_edges, sub_dla_log_nhi,
+                                    want_samples, "population", self._population_dict(population), kwargs)
+
+    def _population_dict(self, population):
+        """``process_population``'s ``population`` in ``_run_multi``'s working form (None stays None)."""
         pop = None
         if population is not None:
             known = {"z_edges", "log_nhi_edges", "log_nhi_samples", "log_priors_no_dla", "log_priors_dla",
@@ -517,8 +561,40 @@ class Engine:
                        p_thresh_spec=float(population.get("p_thresh_spec", 0.05)))
             if pop["z_edges"].size < 1 or pop["log_nhi_edges"].size < 1:
                 raise ValueError("population edges must not be empty")
+        return pop
+
+    def process_levels(self, packed: dict, max_dlas: int = 1, population=None, sub_dla=None, log_nhi_samples=None,
+                       z_edges=None, log_nhi_edges=None, sub_dla_log_nhi=None, want_samples: bool = True,
+                       levels=None, **kwargs) -> dict:
+        """``process_population`` (its arguments pass through; every array of it comes back bit for bit) plus
+        the population statistics over every level of the multi-DLA search (gpdla_engine_process_levels;
+        DESIGN.md section 18): sample j of level d carries d absorbers, its own and those of its base chain, and
+        each is binned with the sample's normalised mass pi_{d,j}.  ``levels`` names the halves wanted,
+        ``("planes", "split")``; the default is every half the call has the inputs for (a summary grid,
+        ``population``), and ``levels=()`` is ``process_population`` itself.  Adds
+
+        ``bin_planes_levels`` (Q x D x 5 x nz x nn)        "planes": per level, ``bin_planes``'s five sums over the
+                                                           (sample, slot) pairs of each bin of the summary grid
+        ``population_level_posteriors`` (D x Q)            "split": P_d, the posterior of exactly d DLAs
+        ``population_level_poisson`` (Q x D x nz x nn)     per level ``population_poisson`` with p = P_d pi_{d,j},
+                                                           added to the bin of every slot of the sample
+        ``population_level_large_inds`` / ``_probs`` (Q x D x 8), ``_bins`` (Q x D x 8 x 4)   the samples with
+                                                           p >= p_switch and a slot inside the grid: index, p and
+                                                           one bin per slot (-1 outside the grid or beyond d)
+        Level 1 of the planes is ``bin_planes`` bit for bit."""
+        have = (("planes",) if z_edges is not None else ()) + (("split",) if population is not None else ())
+        halves = have if levels is None else tuple(levels)
+        if set(halves) - {"planes", "split"}:
+            raise ValueError("levels names 'planes' and / or 'split'")
         return self._process_models(packed, max_dlas, sub_dla, log_nhi_samples, z_edges, log_nhi_edges, sub_dla_log_nhi,
-                                    want_samples, "population", pop, kwargs)
+                                    want_samples, "population", self._population_dict(population), kwargs,
+                                    levels=halves)
+
+    def level_population_stats(self) -> dict:
+        """gpdla_engine_get_level_population_stats: cumulative ms and count of the level-population launches."""
+        ms, n = C.c_double(0.0), C.c_int64(0)
+        L.check(self.lib.gpdla_engine_get_level_population_stats(self._h, C.byref(ms), C.byref(n)))
+        return dict(level_population_ms=ms.value, level_population_launches=n.value)
 
     def population_stats(self) -> dict:
         """gpdla_engine_get_population_stats: cumulative ms and count of the population launches."""
@@ -709,6 +785,83 @@ def population_split(log_likelihoods, offset_samples, log_nhi_samples, min_z, ma
         L.ptr(plane), L.ptr(inds, C.c_int32), L.ptr(probs), L.ptr(bins, C.c_int32)))
     return dict(population_poisson=plane, population_large_inds=inds, population_large_probs=probs,
                 population_large_bins=bins)
+
+
+def _level_rows(log_likelihoods, offset_samples, log_nhi_samples, min_z, max_z, base_sample_inds):
+    """The arguments the two stand-alone level kernels share, as contiguous arrays."""
+    ll = np.ascontiguousarray(log_likelihoods, dtype=np.float64)
+    if ll.ndim == 2:
+        ll = ll[None]
+    if ll.ndim != 3:
+        raise ValueError("log_likelihoods must be rows x S or levels x rows x S")
+    levels, rows, S = ll.shape
+    off = np.ascontiguousarray(offset_samples, dtype=np.float64).ravel()
+    lognhi = np.ascontiguousarray(log_nhi_samples, dtype=np.float64).ravel()
+    if not off.size == lognhi.size == S:
+        raise ValueError("sample arrays must have S entries")
+    zmin = np.ascontiguousarray(np.broadcast_to(np.asarray(min_z, dtype=np.float64), (rows,)))
+    zmax = np.ascontiguousarray(np.broadcast_to(np.asarray(max_z, dtype=np.float64), (rows,)))
+    base = None
+    if base_sample_inds is not None:
+        base = np.ascontiguousarray(base_sample_inds, dtype=np.int32)
+        if base.shape != (max(levels - 1, 0), rows, S):
+            raise ValueError(f"base_sample_inds must be {(levels - 1, rows, S)}")
+    return ll, off, lognhi, zmin, zmax, base
+
+
+def level_planes(log_likelihoods, offset_samples, log_nhi_samples, nhi_samples, min_z, max_z, z_edges, log_nhi_edges,
+                 base_sample_inds=None, device: int = 0) -> np.ndarray:
+    """The level-planes kernel alone (gpdla_level_planes_f64) on host arrays, with ``posterior_summary``'s
+    inputs: ``log_likelihoods`` levels x rows x S, ``base_sample_inds`` (levels - 1) x rows x S (0-based, -1 =
+    none).  Returns ``bin_planes_levels``, rows x levels x 5 x nz x nn."""
+    ll, off, lognhi, zmin, zmax, base = _level_rows(log_likelihoods, offset_samples, log_nhi_samples, min_z, max_z,
+                                                    base_sample_inds)
+    levels, rows, S = ll.shape
+    nhi = np.ascontiguousarray(nhi_samples, dtype=np.float64).ravel()
+    if nhi.size != S:
+        raise ValueError("sample arrays must have S entries")
+    ez = np.ascontiguousarray(z_edges, dtype=np.float64).ravel()
+    en = np.ascontiguousarray(log_nhi_edges, dtype=np.float64).ravel()
+    nz, nn = ez.size - 1, en.size - 1
+    spec = L.SummarySpec(log_nhi_samples=L.ptr(lognhi), num_z_bins=nz, num_nhi_bins=nn, z_edges=L.ptr(ez),
+                         log_nhi_edges=L.ptr(en))
+    planes = np.zeros((rows, levels, L.SUMMARY_PLANES, max(nz, 1), max(nn, 1)))
+    L.check(L.load().gpdla_level_planes_f64(
+        device, L.ptr(ll), rows, S, S, L.ptr(off), L.ptr(lognhi), L.ptr(nhi), L.ptr(zmin), L.ptr(zmax),
+        L.ptr(base, C.c_int32) if base is not None and base.size else None, levels, C.byref(spec), L.ptr(planes)))
+    return planes
+
+
+def population_split_levels(log_likelihoods, offset_samples, log_nhi_samples, min_z, max_z, level_posteriors, z_edges,
+                            log_nhi_edges, base_sample_inds=None, p_thresh_sample: float = 1e-4,
+                            p_switch: float = 0.25, device: int = 0) -> dict:
+    """The level-split kernel alone (gpdla_population_split_levels_f64) on host arrays: ``log_likelihoods``
+    levels x rows x S, ``base_sample_inds`` (levels - 1) x rows x S, ``level_posteriors`` levels x rows (an
+    input).  Returns ``Engine.process_levels``'s ``population_level_poisson`` (rows x levels x nz x nn),
+    ``population_level_large_inds`` / ``_probs`` (rows x levels x 8) and ``_bins`` (rows x levels x 8 x 4)."""
+    ll, off, lognhi, zmin, zmax, base = _level_rows(log_likelihoods, offset_samples, log_nhi_samples, min_z, max_z,
+                                                    base_sample_inds)
+    levels, rows, S = ll.shape
+    P = np.ascontiguousarray(level_posteriors, dtype=np.float64).reshape(-1, rows) if rows else np.zeros((levels, 0))
+    if P.shape != (levels, rows):
+        raise ValueError(f"level_posteriors must be {(levels, rows)}")
+    ez = np.ascontiguousarray(z_edges, dtype=np.float64).ravel()
+    en = np.ascontiguousarray(log_nhi_edges, dtype=np.float64).ravel()
+    nz, nn = ez.size - 1, en.size - 1
+    spec = L.PopulationSpec(log_nhi_samples=L.ptr(lognhi), num_z_bins=nz, num_nhi_bins=nn, z_edges=L.ptr(ez),
+                            log_nhi_edges=L.ptr(en), p_thresh_sample=float(p_thresh_sample), p_switch=float(p_switch),
+                            p_thresh_spec=0.05, log_priors_no_dla=None, log_priors_dla=None, log_priors_lls=None)
+    NL = L.POPULATION_MAX_LARGE
+    plane = np.zeros((rows, levels, max(nz, 1), max(nn, 1)))
+    inds = np.full((rows, levels, NL), -1, dtype=np.int32)
+    bins = np.full((rows, levels, NL, L.MAX_DLAS), -1, dtype=np.int32)
+    probs = np.full((rows, levels, NL), np.nan)
+    L.check(L.load().gpdla_population_split_levels_f64(
+        device, L.ptr(ll), rows, S, S, L.ptr(off), L.ptr(lognhi), L.ptr(zmin), L.ptr(zmax),
+        L.ptr(base, C.c_int32) if base is not None and base.size else None, levels, L.ptr(P), C.byref(spec),
+        L.ptr(plane), L.ptr(inds, C.c_int32), L.ptr(probs), L.ptr(bins, C.c_int32)))
+    return dict(population_level_poisson=plane, population_level_large_inds=inds, population_level_large_probs=probs,
+                population_level_large_bins=bins)
 
 
 def poisson_binomial_pmf_csr(probs, offsets, device: int = 0) -> np.ndarray:

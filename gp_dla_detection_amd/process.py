@@ -226,19 +226,32 @@ def _select(spectra, test_ind):
 
 
 def _summary_grid(summaries):
-    """``summaries`` of process_qsos -> None (off) or (z_edges, log_nhi_edges), both None for MAP only."""
+    """``summaries`` of process_qsos -> None (off) or (z_edges, log_nhi_edges), both None for MAP only.  The
+    dict may also hold ``levels`` ("first", the default, or "all": ``_summary_levels``), which needs the grid."""
     if summaries is None or summaries is False:
         return None
     if summaries is True:
         return None, None
-    if not isinstance(summaries, dict) or set(summaries) - {"z_edges", "log_nhi_edges"}:
-        raise ValueError("summaries must be None, True or dict(z_edges=..., log_nhi_edges=...)")
+    if not isinstance(summaries, dict) or set(summaries) - {"z_edges", "log_nhi_edges", "levels"}:
+        raise ValueError("summaries must be None, True or dict(z_edges=..., log_nhi_edges=..., levels=...)")
+    if summaries.get("levels", "first") not in LEVELS:
+        raise ValueError(f"summaries levels must be one of {LEVELS}")
     ez, en = summaries.get("z_edges"), summaries.get("log_nhi_edges")
     if (ez is None) != (en is None):
         raise ValueError("summaries needs both z_edges and log_nhi_edges, or neither")
     if ez is None:
+        if summaries.get("levels", "first") == "all":
+            raise ValueError("summaries levels='all' needs z_edges and log_nhi_edges")
         return None, None
     return np.ascontiguousarray(ez, dtype=np.float64).ravel(), np.ascontiguousarray(en, dtype=np.float64).ravel()
+
+
+LEVELS = ("first", "all")    # which levels the binned masses / the population split count
+
+
+def _summary_levels(summaries) -> bool:
+    """True when ``summaries`` asks for the binned masses of every level (``levels="all"``)."""
+    return _summary_grid(summaries) is not None and isinstance(summaries, dict) and summaries.get("levels") == "all"
 
 
 POPULATION_DEFAULTS = dict(p_thresh_sample=1e-4, p_switch=0.25)   # calc_cddf.py:47,50
@@ -248,10 +261,11 @@ POPULATION_MAX_BINS = 1024   # GPDLA_SUMMARY_MAX_BINS
 
 def _population_spec(population):
     """``population`` of process_qsos -> None (off) or dict(z_edges, log_nhi_edges, p_thresh_sample, p_switch),
-    checked as the library checks them."""
+    checked as the library checks them; with ``levels="all"`` (every level of the multi-DLA search, not the
+    first alone) the dict also holds ``levels``."""
     if population is None or population is False:
         return None
-    keys = {"z_edges", "log_nhi_edges"} | set(POPULATION_DEFAULTS)
+    keys = {"z_edges", "log_nhi_edges", "levels"} | set(POPULATION_DEFAULTS)
     if not isinstance(population, dict) or set(population) - keys:
         raise ValueError(f"population must be None or a dict of {sorted(keys)}")
     if "z_edges" not in population or "log_nhi_edges" not in population:
@@ -271,6 +285,10 @@ def _population_spec(population):
         raise ValueError(f"p_switch must be finite and >= 1/{POPULATION_MAX_LARGE}")
     if not 0.0 <= pop["p_thresh_sample"] < pop["p_switch"]:
         raise ValueError("p_thresh_sample must lie in [0, p_switch)")
+    if population.get("levels", "first") not in LEVELS:
+        raise ValueError(f"population levels must be one of {LEVELS}")
+    if population.get("levels") == "all":
+        pop["levels"] = "all"
     return pop
 
 
@@ -328,12 +346,35 @@ def _engine_compute(model: dict, samples: dict, packed: dict, params: Parameters
     ``summaries`` the posterior summaries as well (Engine.process_summaries), the sample arrays only if
     ``save_samples``.  ``sub_dla`` (the normalised dict of ``_sub_dla_spec``) adds the sub-DLA model's arrays
     (Engine.process_models); ``forest`` (the settings dict) is set on the engine for this call and cleared
-    after it.  ``population`` (the dict ``_compute_kwargs`` documents) adds Engine.process_population's arrays."""
+    after it.  ``population`` (the dict ``_compute_kwargs`` documents) adds Engine.process_population's arrays;
+    ``levels="all"`` in either dict routes the call through Engine.process_levels for that half."""
     grid = _summary_grid(summaries)
+    halves = (("planes",) if _summary_levels(summaries) else ()) + \
+             (("split",) if population is not None and population.get("levels") == "all" else ())
     eng = engine or Engine(model, samples, params, device=device)
     try:
         if forest is not None:
             eng.set_forest(forest)
+        if halves:
+            if "log_nhi_samples" not in samples:
+                raise ValueError("levels='all' needs samples['log_nhi_samples']")
+            popd = None
+            if population is not None:
+                popd = {k: v for k, v in population.items() if k != "levels"}
+                popd["log_nhi_samples"] = samples["log_nhi_samples"]
+            res = eng.process_levels(
+                packed, max_dlas, population=popd, sub_dla=None if sub_dla is None else sub_dla["nhi"],
+                log_nhi_samples=samples["log_nhi_samples"] if grid is not None else None,
+                z_edges=grid[0] if grid is not None else None, log_nhi_edges=grid[1] if grid is not None else None,
+                sub_dla_log_nhi=None if sub_dla is None else sub_dla["log_nhi"], want_samples=save_samples,
+                levels=halves)
+            if max_dlas == 1:   # Engine.process's shapes: no level axis, no multi-DLA variables
+                res["log_likelihoods_dla"] = res["log_likelihoods_dla"][0]
+                if "sample_log_likelihoods_dla" in res:
+                    res["sample_log_likelihoods_dla"] = res["sample_log_likelihoods_dla"][0]
+                res.pop("base_sample_inds", None)
+                res.pop("max_dlas", None)
+            return res
         if population is not None:
             if "log_nhi_samples" not in samples:
                 raise ValueError("population needs samples['log_nhi_samples']")
@@ -503,6 +544,33 @@ def _finish_population(out: dict, res: dict, pop: dict) -> dict:
     return out
 
 
+def _finish_levels(out: dict, res: dict, summaries, pop: dict | None, max_dlas: int) -> dict:
+    """Add the LEVEL_POPULATION_VARIABLES a ``levels="all"`` run produced.  ``res`` holds Engine.process_levels's
+    arrays; the level posteriors become Q x D, the sample indices and the flat bins 1-based doubles with
+    0 = none, like ``population_large_inds``."""
+    Q, D = np.asarray(out["log_likelihoods_no_dla"]).size, int(max_dlas)
+    if _summary_levels(summaries):
+        ez, en = _summary_grid(summaries)
+        planes = np.asarray(res["bin_planes_levels"], dtype=np.float64)
+        if planes.shape != (Q, D, 5, ez.size - 1, en.size - 1):
+            raise ValueError(f"bin_planes_levels must be {(Q, D, 5, ez.size - 1, en.size - 1)}")
+        out["bin_planes_levels"] = planes
+    if pop is not None and pop.get("levels") == "all":
+        nz, nn = pop["z_edges"].size - 1, pop["log_nhi_edges"].size - 1
+        shapes = dict(population_level_posteriors=(D, Q), population_level_poisson=(Q, D, nz, nn),
+                      population_level_large_inds=(Q, D, POPULATION_MAX_LARGE),
+                      population_level_large_probs=(Q, D, POPULATION_MAX_LARGE),
+                      population_level_large_bins=(Q, D, POPULATION_MAX_LARGE, 4))
+        for key, shape in shapes.items():
+            v = np.asarray(res[key])
+            if v.shape != shape:
+                raise ValueError(f"{key} must be {shape}")
+            if key in ("population_level_large_inds", "population_level_large_bins"):
+                v = v.astype(np.float64) + 1.0
+            out[key] = np.ascontiguousarray(v.T if key == "population_level_posteriors" else v, dtype=np.float64)
+    return out
+
+
 def _finish(res: dict, z_qsos, prior: dict | None, params: Parameters, metadata: dict | None,
             max_dlas: int = 1, summaries=None, sub=None, forest=None) -> dict:
     """process_qsos.m:122-132, 150-155, 202-232: priors, posteriors and the saved scalars."""
@@ -583,7 +651,18 @@ def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
     output gains POPULATION_VARIABLES (catalog.py's ``split_distributions`` and the functions after it consume
     them).  It combines with every other keyword; without it every variable is as before, bit for bit.  A
     ``compute`` replacement receives ``population=`` (the edges, the thresholds and ``log_priors_no_dla`` [Q],
-    ``log_priors_dla`` [D x Q], ``log_priors_lls`` [Q] or None) only when it is set."""
+    ``log_priors_dla`` [D x Q], ``log_priors_lls`` [Q] or None) only when it is set.
+
+    ``levels="all"`` inside ``summaries`` (with a grid) and / or ``population`` counts every absorber of every
+    level of the multi-DLA search instead of the level-1 samples alone (Engine.process_levels; DESIGN.md
+    section 18): sample j of level d carries d absorbers, its own and its base chain's.  Every variable above
+    is still written, bit for bit; the output gains ``bin_planes_levels`` (Q x D x 5 x nz x nn) from
+    ``summaries`` and, from ``population``, ``population_level_posteriors`` (Q x D: Pr(exactly d DLAs)),
+    ``population_level_poisson`` (Q x D x nz x nn), ``population_level_large_inds`` / ``_probs`` (Q x D x 8) and
+    ``population_level_large_bins`` (Q x D x 8 x 4; indices and bins 1-based, 0 = none) --
+    LEVEL_POPULATION_VARIABLES, which catalog.py's functions read with ``levels="all"``.  The default
+    ``levels="first"`` is the run without the key.  A ``compute`` replacement finds ``levels="all"`` inside the
+    ``summaries`` / ``population`` dicts it already gets."""
     if not 1 <= int(max_dlas) <= 4:
         raise ValueError("max_dlas must be 1..4")
     pop = _population_spec(population)
@@ -606,6 +685,7 @@ def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
     out = _finish(res, packed["z_qsos"], prior, params, metadata, max_dlas, summaries, sub, fst)
     if pop is not None:
         _finish_population(out, res, pop)
+    _finish_levels(out, res, summaries, pop, max_dlas)
     if test_ind is not None:
         out["test_ind"] = np.asarray(test_ind)
     return out
@@ -638,6 +718,11 @@ MEAN_FLUX_SCOPE_VARIABLES = ("mean_flux_scope",)
 POPULATION_VARIABLES = ("population_poisson", "population_large_inds", "population_large_probs",
                         "population_large_bins", "population_p_dlas", "population_z_edges",
                         "population_log_nhi_edges", "population_p_thresh_sample", "population_p_switch")
+# what ``levels="all"`` in ``summaries`` (the first) / ``population`` (the rest) saves besides: the reductions
+# over every absorber of every multi-DLA level; catalog.py reads them with levels="all"
+LEVEL_POPULATION_VARIABLES = ("bin_planes_levels", "population_level_posteriors", "population_level_poisson",
+                              "population_level_large_inds", "population_level_large_probs",
+                              "population_level_large_bins")
 
 
 def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
@@ -660,11 +745,12 @@ def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
     SUB_DLA_VARIABLES (``model_posteriors`` is then Q x (1 + D + 1), the sub-DLA column last, so h5py's
     ``model_posteriors[2]`` still reads "exactly two DLAs", calc_cddf.py:67), one with ``forest`` the
     FOREST_VARIABLES (and, with a ``mean_flux_scope`` other than "mu", MEAN_FLUX_SCOPE_VARIABLES), one
-    with ``population`` the POPULATION_VARIABLES."""
+    with ``population`` the POPULATION_VARIABLES, one with ``levels="all"`` the LEVEL_POPULATION_VARIABLES
+    (h5py sees ``bin_planes_levels`` as (nn, nz, 5, D, Q))."""
     mat = {}
     multi = int(np.ravel(out.get("max_dlas", 1))[0]) > 1
     for key in (PROCESSED_VARIABLES + (MULTI_DLA_VARIABLES if multi else ()) + SUMMARY_VARIABLES + SUB_DLA_VARIABLES +
-                FOREST_VARIABLES + MEAN_FLUX_SCOPE_VARIABLES + POPULATION_VARIABLES):
+                FOREST_VARIABLES + MEAN_FLUX_SCOPE_VARIABLES + POPULATION_VARIABLES + LEVEL_POPULATION_VARIABLES):
         if key not in out:
             continue
         v = out[key]
@@ -858,7 +944,7 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
     ``sub_dla`` / ``forest`` as in ``process_qsos``: ``sub_dla`` on one GPU only (``world`` > 1 raises
     NotImplementedError: its arrays are not gathered); ``forest`` alone passes through to every rank's
     engine.  ``population`` as in ``process_qsos``, on one GPU only (``world`` > 1 raises NotImplementedError:
-    its arrays are not gathered)."""
+    its arrays are not gathered); ``levels="all"`` in either dict likewise."""
     import time
     if not 1 <= int(max_dlas) <= 4:
         raise ValueError("max_dlas must be 1..4")
@@ -942,6 +1028,7 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
         out = _finish(res, z_all, prior, params, meta, max_dlas, summaries, sub, fst)
         if pop is not None:
             _finish_population(out, res, pop)
+        _finish_levels(out, res, summaries, pop, max_dlas)
         out["test_ind"] = tind
         if save:
             save_processed_qsos(path, out)

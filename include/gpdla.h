@@ -449,6 +449,78 @@ int gpdla_population_split_f64(int32_t device, const double* ll, int64_t rows, i
 int gpdla_poisson_binomial_pmf_f64(int32_t device, const double* probs, const int64_t* offsets, int64_t num_bins,
                                    double* pmf);
 
+/* ---- Population statistics over every multi-DLA level --------------------------
+ * The reductions above count the level-1 samples only.  These count every absorber of every level of a
+ * max_dlas = D run, under section 12's model.  For spectrum q, level d = 1..D and sample j (caller order):
+ *   masses      pi_{d,j} = w / W over level d's row, w = exp(l_d[j] - max over the non-NaN entries) (NaN ->
+ *               0), W = sum w, every pi 0 if W is 0 or not finite; formed by the partial sums and trees of
+ *               the level-1 reductions, so pi_{1,j} is their pi_j bit for bit
+ *   absorbers   sample (d, j) carries d of them: slot 0 is sample j itself, slots 1..d-1 its base chain
+ *               b1 = base_sample_inds[d-2][q][j], b2 = base_sample_inds[d-3][q][b1], ... (the walk of
+ *               map_z_dlas).  Slot i has z = min_z + (max_z - min_z) offset_i (product and sum rounded
+ *               separately), log N_i and N_i of its sample and the bin the level-1 rule gives those.  A chain
+ *               that meets -1 or an index outside [0, S) voids every slot of the sample: it contributes
+ *               nothing, though its pi still counts in W
+ *   posteriors  P_d = exp(lp_d - max) / sum over the models no-DLA, DLA 1..D (a NaN evidence at a level >= 2
+ *               counts as -inf) and, with the sub-DLA model, sub-DLA: the terms p_dlas is formed from.  Any
+ *               other NaN makes every P_d of the spectrum NaN, and the spectrum contributes nothing.  The
+ *               sub-DLA model is not a DLA and enters none of the sums below
+ *   bin_planes     (summary grid) per level and bin, over the (sample, slot) pairs whose slot falls in the
+ *                  bin: sum pi, pi^2, N pi, N^2 pi, N^2 pi^2 with N the slot's column density, added in
+ *                  (sample index, slot) order.  Level 1's planes are gpdla_summaries.bin_planes bit for bit
+ *   poisson_plane  (population grid) with p = P_d pi_{d,j}: a sample with p_thresh_sample < p < p_switch (or
+ *                  with p >= p_switch and no slot inside the grid: nothing) adds p to the bin of each of its
+ *                  slots inside the grid, in (sample index, slot) order
+ *   large_*        the samples with p >= p_switch and at least one slot inside the grid, by increasing sample
+ *                  index: index (0-based), p and one bin per slot (iz num_nhi_bins + in; -1 for a slot outside
+ *                  the grid or beyond d).  They add nothing to poisson_plane.  sum_j P_d pi_{d,j} <= 1 bounds
+ *                  them by 1 / p_switch <= GPDLA_POPULATION_MAX_LARGE per level.  Unused entries -1 / NaN / -1
+ * The expected number of DLAs of spectrum q in bin b is sum_d P_d sum_{(j, slot) in b} pi_{d,j}; the host
+ * stage treats every (level, sample, slot) as one Bernoulli trial of probability P_d pi_{d,j}.  Every
+ * output is a fixed-order reduction of the spectrum's own rows: repeated calls and any split into device
+ * batches agree bit for bit.  No floating-point atomics. */
+typedef struct gpdla_level_population {
+  int32_t memory;                    /* GPDLA_MEM_HOST or GPDLA_MEM_DEVICE */
+  double* level_posteriors;          /* [D][Q] */
+  double* bin_planes;                /* [Q][D][GPDLA_SUMMARY_PLANES][nz][nn], summary grid; NULL without one */
+  double* poisson_plane;             /* [Q][D][nz][nn], population grid */
+  int32_t* large_inds;               /* [Q][D][GPDLA_POPULATION_MAX_LARGE] */
+  double* large_probs;               /* [Q][D][GPDLA_POPULATION_MAX_LARGE] */
+  int32_t* large_bins;               /* [Q][D][GPDLA_POPULATION_MAX_LARGE][GPDLA_MAX_DLAS] */
+} gpdla_level_population;
+/* gpdla_engine_process_population plus the reductions over every level; with levels NULL it is that call,
+ * bit for bit, and with it every other result is unchanged bit for bit.  The new launches run per device
+ * batch after its last level and the existing summary and population launches.  A half is asked for by its
+ * arrays and either may be absent: bin_planes (it needs spec with a grid), or level_posteriors,
+ * poisson_plane and large_* together (they need pspec, for the priors and the thresholds).  GPDLA_EINVAL for
+ * levels without any array, a half without its spec, a null array of a half asked for or a bad memory kind;
+ * GPDLA_EUNSUPPORTED on int8 and panel-GEMM engines. */
+int gpdla_engine_process_levels(gpdla_engine* engine, const gpdla_spectra* spectra,
+                                const gpdla_multi_dla* multi, const gpdla_sub_dla* sub,
+                                const gpdla_results_multi* results_multi, const gpdla_results_sub* results_sub,
+                                const gpdla_summary_spec* spec, const gpdla_summaries* summaries,
+                                const gpdla_population_spec* pspec, const gpdla_population* population,
+                                const gpdla_level_population* levels);
+/* Cumulative kernel time (HIP events) and count of the level-population launches (a batch's launches are
+ * one span) since create / reset_stats. */
+int gpdla_engine_get_level_population_stats(gpdla_engine* engine, double* ms, int64_t* launches);
+/* The level planes alone, host buffers, with gpdla_posterior_summary_f64's inputs: ll [levels][rows][ld],
+ * base_inds [levels - 1][rows][ld] (NULL when levels = 1); spec must have a grid.  bin_planes is
+ * [rows][levels][GPDLA_SUMMARY_PLANES][nz][nn]. */
+int gpdla_level_planes_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
+                           const double* offset_samples, const double* log_nhi_samples, const double* nhi_samples,
+                           const double* min_z, const double* max_z, const int32_t* base_inds, int32_t levels,
+                           const gpdla_summary_spec* spec, double* bin_planes);
+/* The level split alone, host buffers: as above plus level_posteriors [levels][rows] (an input: each in
+ * [0, 1] or NaN) and the grid and thresholds of spec (its priors and log_nhi_samples are not read).
+ * Outputs as in gpdla_level_population with D = levels, Q = rows. */
+int gpdla_population_split_levels_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
+                                      const double* offset_samples, const double* log_nhi_samples,
+                                      const double* min_z, const double* max_z, const int32_t* base_inds,
+                                      int32_t levels, const double* level_posteriors,
+                                      const gpdla_population_spec* spec, double* poisson_plane,
+                                      int32_t* large_inds, double* large_probs, int32_t* large_bins);
+
 /* voigt MEX replacement (voigt.c:253-304).  Host buffers.  out has n_padded - 6 values. */
 int gpdla_voigt_f64(const double* lambdas, int64_t n_padded, double z, double N,
                     int32_t num_lines, double* out);
