@@ -1145,15 +1145,7 @@ static int validate_summary_grid(const gpdla_summary_spec* spec) {
                      GPDLA_SUMMARY_MAX_BINS);
   if (nz == 0) return GPDLA_OK;
   if (!spec->z_edges || !spec->log_nhi_edges) return set_error(GPDLA_EINVAL, "null summary edge array");
-  for (int ax = 0; ax < 2; ++ax) {
-    const double* ed = ax ? spec->log_nhi_edges : spec->z_edges;
-    const int64_t n = ax ? nn : nz;
-    for (int64_t i = 0; i <= n; ++i)
-      if (!std::isfinite(ed[i]) || (i > 0 && !(ed[i] > ed[i - 1])))
-        return set_error(GPDLA_EINVAL, "%s[%lld] = %g: edges must be finite and strictly increasing",
-                         ax ? "log_nhi_edges" : "z_edges", (long long)i, ed[i]);
-  }
-  return GPDLA_OK;
+  return validate_grid_edges("", nz, nn, spec->z_edges, spec->log_nhi_edges);
 }
 
 // gpdla_engine_process_multi, and with spec / sums gpdla_engine_process_summaries: the summary kernel
@@ -1376,10 +1368,10 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
         if ((rc = grow(&e->d_sub_mz, &e->cap_sub_mz, (size_t)nq * kMaxDlas))) return rc;
         if ((rc = grow(&e->d_sub_mn, &e->cap_sub_mn, (size_t)nq * kMaxDlas))) return rc;
         SummaryArgs sa{};
-        sa.rows = (int32_t)nq; sa.levels = 1; sa.ll = e->d_sub_sll; sa.ld = S; sa.S = S;
-        sa.base = nullptr; sa.ld_base = S;
-        sa.offset = e->d_off_c; sa.log_nhi = e->d_sub_lognhi; sa.nhi = e->d_sub_nhi_c;
-        sa.zmin = e->d_m_zmin; sa.zmax = e->d_m_zmax;
+        sa.r.rows = (int32_t)nq; sa.r.levels = 1; sa.r.ll = e->d_sub_sll; sa.r.ld = S; sa.r.S = S;
+        sa.r.base = nullptr; sa.r.ld_base = S;
+        sa.r.offset = e->d_off_c; sa.r.log_nhi = e->d_sub_lognhi; sa.nhi = e->d_sub_nhi_c;
+        sa.r.zmin = e->d_m_zmin; sa.r.zmax = e->d_m_zmax;
         sa.map_ind = e->d_sub_mind; sa.map_ll = e->d_sub_mll; sa.map_z = e->d_sub_mz; sa.map_n = e->d_sub_mn;
         HIP_TRY(launch_posterior_summary(sa, st));
       }
@@ -1441,6 +1433,17 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
       e->pending.push_back(t6);
     }
 
+    // the batch's rows as the summary and population launches read them, on the grid of each
+    SampleRowsArgs rows_b{};
+    rows_b.rows = (int32_t)nq; rows_b.levels = D; rows_b.ll = e->d_m_sll; rows_b.ld = S; rows_b.S = S;
+    rows_b.base = D > 1 ? e->d_m_base : nullptr; rows_b.ld_base = S;
+    rows_b.offset = e->d_off_c; rows_b.zmin = e->d_m_zmin; rows_b.zmax = e->d_m_zmax;
+    auto on_grid = [&](const double* log_nhi, int nz, int nn, const double* edges) {
+      SampleRowsArgs r = rows_b;
+      r.log_nhi = log_nhi; r.nz = nz; r.nn = nn; r.z_edges = edges; r.n_edges = nz ? edges + nz + 1 : nullptr;
+      return r;
+    };
+
     if (spec) {
       if ((rc = grow(&e->d_s_ind, &e->cap_s_ind, (size_t)nq * D))) return rc;
       if ((rc = grow(&e->d_s_ll, &e->cap_s_ll, (size_t)nq * D))) return rc;
@@ -1448,11 +1451,7 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
       if ((rc = grow(&e->d_s_n, &e->cap_s_n, (size_t)nq * D * kMaxDlas))) return rc;
       if (nbins && (rc = grow(&e->d_s_planes, &e->cap_s_planes, (size_t)nq * kSummaryPlanes * nbins))) return rc;
       SummaryArgs sa{};
-      sa.rows = (int32_t)nq; sa.levels = D; sa.ll = e->d_m_sll; sa.ld = S; sa.S = S;
-      sa.base = D > 1 ? e->d_m_base : nullptr; sa.ld_base = S;
-      sa.offset = e->d_off_c; sa.log_nhi = e->d_s_lognhi; sa.nhi = e->d_nhi_c;
-      sa.zmin = e->d_m_zmin; sa.zmax = e->d_m_zmax;
-      sa.nz = nzb; sa.nn = nnb; sa.z_edges = e->d_s_edges; sa.n_edges = nbins ? e->d_s_edges + nzb + 1 : nullptr;
+      sa.r = on_grid(e->d_s_lognhi, nzb, nnb, e->d_s_edges); sa.nhi = e->d_nhi_c;
       sa.map_ind = e->d_s_ind; sa.map_ll = e->d_s_ll; sa.map_z = e->d_s_z; sa.map_n = e->d_s_n;
       sa.planes = nbins ? e->d_s_planes : nullptr;
       TimedLaunch t7{};
@@ -1473,6 +1472,7 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
                                (size_t)nq * kSummaryPlanes * nbins * 8, sk, st));
     }
 
+    ModelPosteriorArgs ma{};   // the posterior launches of both population halves
     if (pspec) {
       const size_t NL = kPopulationMaxLarge;
       if ((rc = grow(&e->d_p_pdla, &e->cap_p_pdla, (size_t)nq))) return rc;
@@ -1480,15 +1480,14 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
       if ((rc = grow(&e->d_p_lind, &e->cap_p_lind, (size_t)nq * NL))) return rc;
       if ((rc = grow(&e->d_p_lprob, &e->cap_p_lprob, (size_t)nq * NL))) return rc;
       if ((rc = grow(&e->d_p_lbin, &e->cap_p_lbin, (size_t)nq * NL))) return rc;
-      ModelPosteriorArgs ma{};
       ma.rows = (int32_t)nq; ma.levels = D; ma.ll_null = e->d_m_null; ma.ll_dla = e->d_m_lldla;
       ma.ll_lls = sub ? e->d_sub_ev : nullptr;
       ma.lp_no = e->d_p_lpno + q0; ma.lp_dla = e->d_p_lpdla + q0; ma.lp_lls = sub ? e->d_p_lplls + q0 : nullptr;
       ma.ld_prior = Q; ma.p_dla = e->d_p_pdla;
       PopulationSplitArgs pa{};
-      pa.rows = (int32_t)nq; pa.ll = e->d_m_sll; pa.ld = S; pa.S = S;
-      pa.offset = e->d_off_c; pa.log_nhi = e->d_p_lognhi; pa.zmin = e->d_m_zmin; pa.zmax = e->d_m_zmax;
-      pa.p_dla = e->d_p_pdla; pa.nz = pnz; pa.nn = pnn; pa.z_edges = e->d_p_edges; pa.n_edges = e->d_p_edges + pnz + 1;
+      pa.r = on_grid(e->d_p_lognhi, pnz, pnn, e->d_p_edges);
+      pa.r.levels = 1; pa.r.base = nullptr;   // the level-1 rows alone
+      pa.level_post = e->d_p_pdla; pa.ld_post = nq;
       pa.p_thresh_sample = pspec->p_thresh_sample; pa.p_switch = pspec->p_switch;
       pa.poisson = e->d_p_plane; pa.large_inds = e->d_p_lind; pa.large_probs = e->d_p_lprob; pa.large_bins = e->d_p_lbin;
       TimedLaunch t11{};
@@ -1507,10 +1506,6 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
 
     if (lv) {
       const size_t NL = kPopulationMaxLarge, Ds = (size_t)D;
-      LevelRowsArgs lr{};
-      lr.rows = (int32_t)nq; lr.levels = D; lr.ll = e->d_m_sll; lr.ld = S; lr.S = S;
-      lr.base = D > 1 ? e->d_m_base : nullptr; lr.ld_base = S;
-      lr.offset = e->d_off_c; lr.zmin = e->d_m_zmin; lr.zmax = e->d_m_zmax;
       if (lv_planes && (rc = grow(&e->d_lv_planes, &e->cap_lv_planes, (size_t)nq * Ds * kSummaryPlanes * nbins))) return rc;
       if (lv_split) {
         if ((rc = grow(&e->d_lv_post, &e->cap_lv_post, (size_t)nq * Ds))) return rc;
@@ -1523,20 +1518,14 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
       if ((rc = record_start(e, &t12, 12))) return rc;
       if (lv_planes) {
         LevelPlanesArgs la{};
-        la.r = lr; la.r.log_nhi = e->d_s_lognhi; la.r.nz = nzb; la.r.nn = nnb;
-        la.r.z_edges = e->d_s_edges; la.r.n_edges = e->d_s_edges + nzb + 1;
+        la.r = on_grid(e->d_s_lognhi, nzb, nnb, e->d_s_edges);
         la.nhi = e->d_nhi_c; la.planes = e->d_lv_planes;
         HIP_TRY(launch_level_planes(la, st));
       }
-      if (lv_split) {
-        LevelPosteriorArgs ma{};
-        ma.rows = (int32_t)nq; ma.levels = D; ma.ll_null = e->d_m_null; ma.ll_dla = e->d_m_lldla;
-        ma.ll_lls = sub ? e->d_sub_ev : nullptr;
-        ma.lp_no = e->d_p_lpno + q0; ma.lp_dla = e->d_p_lpdla + q0; ma.lp_lls = sub ? e->d_p_lplls + q0 : nullptr;
-        ma.ld_prior = Q; ma.level_post = e->d_lv_post;
+      if (lv_split) {                      // with a population spec: ma is filled
+        ma.level_post = e->d_lv_post;
         LevelSplitArgs la{};
-        la.r = lr; la.r.log_nhi = e->d_p_lognhi; la.r.nz = pnz; la.r.nn = pnn;
-        la.r.z_edges = e->d_p_edges; la.r.n_edges = e->d_p_edges + pnz + 1;
+        la.r = on_grid(e->d_p_lognhi, pnz, pnn, e->d_p_edges);
         la.level_post = e->d_lv_post; la.ld_post = nq;
         la.p_thresh_sample = pspec->p_thresh_sample; la.p_switch = pspec->p_switch;
         la.poisson = e->d_lv_plane; la.large_inds = e->d_lv_lind; la.large_probs = e->d_lv_lprob; la.large_bins = e->d_lv_lbin;
@@ -1696,26 +1685,14 @@ int gpdla_forest_f64(int32_t device, const double* wavelengths, int64_t n, doubl
   if (rc) return rc;
   if (n == 0) return GPDLA_OK;
   HIP_TRY(hipSetDevice(device));
-  double *d_wl = nullptr, *d_out = nullptr;
-  auto done = [&](int code) {
-    if (d_wl) (void)hipFree(d_wl);
-    if (d_out) (void)hipFree(d_out);
-    return code;
-  };
-#define TRY_F(expr)                                                                                                   \
-  do {                                                                                                                \
-    hipError_t e_ = (expr);                                                                                           \
-    if (e_ != hipSuccess)                                                                                             \
-      return done(set_error(e_ == hipErrorOutOfMemory ? GPDLA_ENOMEM : GPDLA_EDEVICE, "forest: %s failed: %s", #expr, \
-                            hipGetErrorString(e_)));                                                                  \
-  } while (0)
-  TRY_F(hipMalloc((void**)&d_wl, (size_t)n * 8));
-  TRY_F(hipMalloc((void**)&d_out, (size_t)n * 8));
-  TRY_F(hipMemcpy(d_wl, wavelengths, (size_t)n * 8, hipMemcpyHostToDevice));
-  TRY_F(launch_forest_f64(d_wl, n, z_qso, tau_0, beta, num_forest_lines, d_out, nullptr));
-  TRY_F(hipMemcpy(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost));
-#undef TRY_F
-  return done(GPDLA_OK);
+  DeviceStage st;
+  const size_t o_wl = st.carve((size_t)n * 8), o_out = st.carve((size_t)n * 8);
+  HIP_TRY_IN("forest", st.alloc());
+  HIP_TRY_IN("forest", st.upload(o_wl, wavelengths, (size_t)n * 8));
+  HIP_TRY_IN("forest", launch_forest_f64(st.ptr<const double>(o_wl), n, z_qso, tau_0, beta, num_forest_lines,
+                                         st.ptr<double>(o_out), nullptr));
+  HIP_TRY_IN("forest", st.download(out, o_out, (size_t)n * 8));
+  return GPDLA_OK;
 }
 
 int gpdla_engine_get_summary_stats(gpdla_engine* e, double* ms, int64_t* launches) {
@@ -1735,72 +1712,34 @@ int gpdla_posterior_summary_f64(int32_t device, const double* ll, int64_t rows, 
                                 const int32_t* base_inds, int32_t levels, const gpdla_summary_spec* spec,
                                 int32_t* map_sample_inds, double* map_log_likelihoods, double* map_z_dlas,
                                 double* map_log_nhis, double* bin_planes) {
-  if (!ll || !offset_samples || !log_nhi_samples || !nhi_samples || !min_z || !max_z || !spec || !map_sample_inds ||
-      !map_log_likelihoods || !map_z_dlas || !map_log_nhis)
-    return set_error(GPDLA_EINVAL, "null argument");
-  if (rows < 0 || S < 1 || ld < S || rows > INT32_MAX || S > INT32_MAX)
-    return set_error(GPDLA_EINVAL, "rows=%lld S=%lld ld=%lld", (long long)rows, (long long)S, (long long)ld);
-  if (levels < 1 || levels > GPDLA_MAX_DLAS) return set_error(GPDLA_EINVAL, "levels=%d outside 1..%d", levels, GPDLA_MAX_DLAS);
-  if (levels > 1 && !base_inds) return set_error(GPDLA_EINVAL, "levels=%d needs base_inds", levels);
-  int rc = validate_summary_grid(spec);
+  HostSampleRows h{ll, rows, S, ld, offset_samples, log_nhi_samples, nhi_samples, min_z, max_z, base_inds, levels};
+  int rc = h.check(nhi_samples && spec && map_sample_inds && map_log_likelihoods && map_z_dlas && map_log_nhis);
   if (rc) return rc;
-  const int nz = spec->num_z_bins, nn = spec->num_nhi_bins;
-  const size_t nbins = (size_t)nz * nn;
+  if ((rc = validate_summary_grid(spec))) return rc;
+  h.nz = spec->num_z_bins; h.nn = spec->num_nhi_bins; h.z_edges = spec->z_edges; h.n_edges = spec->log_nhi_edges;
+  const size_t nbins = (size_t)h.nz * h.nn;
   if (nbins && !bin_planes) return set_error(GPDLA_EINVAL, "null bin_planes with a grid");
   if ((rc = check_device(device))) return rc;
   if (rows == 0) return GPDLA_OK;
   HIP_TRY(hipSetDevice(device));
-  const size_t R = (size_t)rows, LV = (size_t)levels;
-  // one device allocation, carved in 256-byte steps
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_ll = carve(LV * R * ld * 8), o_base = carve(levels > 1 ? (LV - 1) * R * ld * 4 : 0);
-  const size_t o_off = carve((size_t)S * 8), o_ln = carve((size_t)S * 8), o_nh = carve((size_t)S * 8);
-  const size_t o_zmin = carve(R * 8), o_zmax = carve(R * 8), o_ed = carve((size_t)(nz + nn + 2) * 8);
-  const size_t o_ind = carve(LV * R * 4), o_mll = carve(LV * R * 8);
-  const size_t o_mz = carve(LV * R * kMaxDlas * 8), o_mn = carve(LV * R * kMaxDlas * 8);
-  const size_t o_pl = carve(R * kSummaryPlanes * nbins * 8);
-  char* d = nullptr;
-  auto done = [&](int code) {
-    if (d) (void)hipFree(d);
-    return code;
-  };
-#define TRY_S(expr)                                                                                          \
-  do {                                                                                                       \
-    hipError_t e_ = (expr);                                                                                  \
-    if (e_ != hipSuccess)                                                                                    \
-      return done(set_error(e_ == hipErrorOutOfMemory ? GPDLA_ENOMEM : GPDLA_EDEVICE, "posterior_summary: %s failed: %s", \
-                            #expr, hipGetErrorString(e_)));                                                  \
-  } while (0)
-  TRY_S(hipMalloc((void**)&d, off));
-  TRY_S(hipMemcpy(d + o_ll, ll, LV * R * ld * 8, hipMemcpyHostToDevice));
-  if (levels > 1) TRY_S(hipMemcpy(d + o_base, base_inds, (LV - 1) * R * ld * 4, hipMemcpyHostToDevice));
-  TRY_S(hipMemcpy(d + o_off, offset_samples, (size_t)S * 8, hipMemcpyHostToDevice));
-  TRY_S(hipMemcpy(d + o_ln, log_nhi_samples, (size_t)S * 8, hipMemcpyHostToDevice));
-  TRY_S(hipMemcpy(d + o_nh, nhi_samples, (size_t)S * 8, hipMemcpyHostToDevice));
-  TRY_S(hipMemcpy(d + o_zmin, min_z, R * 8, hipMemcpyHostToDevice));
-  TRY_S(hipMemcpy(d + o_zmax, max_z, R * 8, hipMemcpyHostToDevice));
-  if (nbins) {
-    TRY_S(hipMemcpy(d + o_ed, spec->z_edges, (size_t)(nz + 1) * 8, hipMemcpyHostToDevice));
-    TRY_S(hipMemcpy(d + o_ed + (size_t)(nz + 1) * 8, spec->log_nhi_edges, (size_t)(nn + 1) * 8, hipMemcpyHostToDevice));
-  }
+  const size_t LR = (size_t)levels * rows;
+  DeviceStage st;
+  h.carve(st);
+  const size_t o_ind = st.carve(LR * 4), o_mll = st.carve(LR * 8), o_mz = st.carve(LR * kMaxDlas * 8);
+  const size_t o_mn = st.carve(LR * kMaxDlas * 8), o_pl = st.carve((size_t)rows * kSummaryPlanes * nbins * 8);
   SummaryArgs sa{};
-  sa.rows = (int32_t)rows; sa.levels = levels; sa.ll = (const double*)(d + o_ll); sa.ld = ld; sa.S = S;
-  sa.base = levels > 1 ? (const int32_t*)(d + o_base) : nullptr; sa.ld_base = ld;
-  sa.offset = (const double*)(d + o_off); sa.log_nhi = (const double*)(d + o_ln); sa.nhi = (const double*)(d + o_nh);
-  sa.zmin = (const double*)(d + o_zmin); sa.zmax = (const double*)(d + o_zmax);
-  sa.nz = nz; sa.nn = nn; sa.z_edges = (const double*)(d + o_ed); sa.n_edges = (const double*)(d + o_ed) + nz + 1;
-  sa.map_ind = (int32_t*)(d + o_ind); sa.map_ll = (double*)(d + o_mll);
-  sa.map_z = (double*)(d + o_mz); sa.map_n = (double*)(d + o_mn);
-  sa.planes = nbins ? (double*)(d + o_pl) : nullptr;
-  TRY_S(launch_posterior_summary(sa, nullptr));
-  TRY_S(hipMemcpy(map_sample_inds, d + o_ind, LV * R * 4, hipMemcpyDeviceToHost));
-  TRY_S(hipMemcpy(map_log_likelihoods, d + o_mll, LV * R * 8, hipMemcpyDeviceToHost));
-  TRY_S(hipMemcpy(map_z_dlas, d + o_mz, LV * R * kMaxDlas * 8, hipMemcpyDeviceToHost));
-  TRY_S(hipMemcpy(map_log_nhis, d + o_mn, LV * R * kMaxDlas * 8, hipMemcpyDeviceToHost));
-  if (nbins) TRY_S(hipMemcpy(bin_planes, d + o_pl, R * kSummaryPlanes * nbins * 8, hipMemcpyDeviceToHost));
-#undef TRY_S
-  return done(GPDLA_OK);
+  HIP_TRY_IN("posterior_summary", st.alloc());
+  HIP_TRY_IN("posterior_summary", h.upload(st, &sa.r, &sa.nhi));
+  sa.map_ind = st.ptr<int32_t>(o_ind); sa.map_ll = st.ptr<double>(o_mll);
+  sa.map_z = st.ptr<double>(o_mz); sa.map_n = st.ptr<double>(o_mn);
+  sa.planes = nbins ? st.ptr<double>(o_pl) : nullptr;
+  HIP_TRY_IN("posterior_summary", launch_posterior_summary(sa, nullptr));
+  HIP_TRY_IN("posterior_summary", st.download(map_sample_inds, o_ind, LR * 4));
+  HIP_TRY_IN("posterior_summary", st.download(map_log_likelihoods, o_mll, LR * 8));
+  HIP_TRY_IN("posterior_summary", st.download(map_z_dlas, o_mz, LR * kMaxDlas * 8));
+  HIP_TRY_IN("posterior_summary", st.download(map_log_nhis, o_mn, LR * kMaxDlas * 8));
+  if (nbins) HIP_TRY_IN("posterior_summary", st.download(bin_planes, o_pl, (size_t)rows * kSummaryPlanes * nbins * 8));
+  return GPDLA_OK;
 }
 
 int gpdla_resample_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld, const double* u,
@@ -1814,33 +1753,20 @@ int gpdla_resample_f64(int32_t device, const double* ll, int64_t rows, int64_t S
   if (rc) return rc;
   if (rows == 0) return GPDLA_OK;
   HIP_TRY(hipSetDevice(device));
-  double *d_ll = nullptr, *d_u = nullptr, *d_c = nullptr;
-  int32_t* d_b = nullptr;
-  auto done = [&](int code) {
-    for (void* p : {(void*)d_ll, (void*)d_u, (void*)d_c, (void*)d_b})
-      if (p) (void)hipFree(p);
-    return code;
-  };
-#define TRY_R(expr)                                                                                         \
-  do {                                                                                                      \
-    hipError_t e_ = (expr);                                                                                 \
-    if (e_ != hipSuccess)                                                                                   \
-      return done(set_error(e_ == hipErrorOutOfMemory ? GPDLA_ENOMEM : GPDLA_EDEVICE, "resample: %s failed: %s", \
-                            #expr, hipGetErrorString(e_)));                                                 \
-  } while (0)
-  TRY_R(hipMalloc((void**)&d_ll, (size_t)rows * ld * 8));
-  TRY_R(hipMalloc((void**)&d_u, (size_t)S * 8));
-  TRY_R(hipMalloc((void**)&d_b, (size_t)rows * S * 4));
-  if (S > GPDLA_RESAMPLE_LDS) TRY_R(hipMalloc((void**)&d_c, (size_t)rows * S * 8));
-  TRY_R(hipMemcpy(d_ll, ll, (size_t)rows * ld * 8, hipMemcpyHostToDevice));
-  TRY_R(hipMemcpy(d_u, u, (size_t)S * 8, hipMemcpyHostToDevice));
+  DeviceStage st;
+  const size_t o_ll = st.carve((size_t)rows * ld * 8), o_u = st.carve((size_t)S * 8), o_b = st.carve((size_t)rows * S * 4);
+  const size_t o_c = st.carve(S > GPDLA_RESAMPLE_LDS ? (size_t)rows * S * 8 : 0);
+  HIP_TRY_IN("resample", st.alloc());
+  HIP_TRY_IN("resample", st.upload(o_ll, ll, (size_t)rows * ld * 8));
+  HIP_TRY_IN("resample", st.upload(o_u, u, (size_t)S * 8));
   ResampleArgs ra{};
-  ra.rows = (int32_t)rows; ra.ll = d_ll; ra.ld = ld; ra.S = S; ra.u = d_u; ra.cws = d_c; ra.base_inds = d_b;
-  TRY_R(launch_resample(ra, nullptr));
-  TRY_R(hipMemcpy(out_inds, d_b, (size_t)rows * S * 4, hipMemcpyDeviceToHost));
-#undef TRY_R
-  return done(GPDLA_OK);
+  ra.rows = (int32_t)rows; ra.ll = st.ptr<const double>(o_ll); ra.ld = ld; ra.S = S; ra.u = st.ptr<const double>(o_u);
+  ra.cws = S > GPDLA_RESAMPLE_LDS ? st.ptr<double>(o_c) : nullptr; ra.base_inds = st.ptr<int32_t>(o_b);
+  HIP_TRY_IN("resample", launch_resample(ra, nullptr));
+  HIP_TRY_IN("resample", st.download(out_inds, o_b, (size_t)rows * S * 4));
+  return GPDLA_OK;
 }
+
 
 // ---------------------------------------------------------------------------------------------
 // device buffer helpers

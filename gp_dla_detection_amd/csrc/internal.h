@@ -18,6 +18,15 @@
                                 __FILE__, __LINE__);                                        \
   } while (0)
 
+// The same for the stand-alone calls, whose messages begin with the call's name: "<ctx>: <expr> failed: ..."
+#define HIP_TRY_IN(ctx, expr)                                                                       \
+  do {                                                                                              \
+    hipError_t e_ = (expr);                                                                         \
+    if (e_ != hipSuccess)                                                                           \
+      return ::gpdla::set_error(e_ == hipErrorOutOfMemory ? GPDLA_ENOMEM : GPDLA_EDEVICE,           \
+                                ctx ": %s failed: %s", #expr, hipGetErrorString(e_));               \
+  } while (0)
+
 namespace gpdla {
 
 // C-ABI error reporting shared by the translation units (engine.hip): sets gpdla_last_error()
@@ -509,11 +518,12 @@ hipError_t launch_multi_level(int K, const MultiLevelArgs& a, hipStream_t s);
 hipError_t launch_resample(const ResampleArgs& a, hipStream_t s);
 hipError_t launch_multi_reduce(const MultiReduceArgs& a, hipStream_t s);
 
-// ---- posterior summaries (posterior_summary.hip): MAP sample and chain parameters per (row, level),
-// binned normalised masses of level 1
+// ---- the sample rows the summary and population kernels reduce (row_posterior.h), and the grid they bin on
 constexpr int kSummaryPlanes = 5;        // sum pi, pi^2, N pi, N^2 pi, N^2 pi^2 per bin
 constexpr int kSummaryMaxBins = 1024;
-struct SummaryArgs {
+constexpr int kPopulationMaxLarge = 8;
+constexpr int kPmfChunk = 512;           // trials per chunk polynomial
+struct SampleRowsArgs {
   int32_t rows, levels;
   const double* ll;              // [levels][rows][ld], caller's sample order
   int64_t ld, S;
@@ -521,12 +531,24 @@ struct SummaryArgs {
   int64_t ld_base;
   const double* offset;          // [S] caller order
   const double* log_nhi;         // [S]
-  const double* nhi;             // [S]
   const double* zmin;            // [rows]
   const double* zmax;            // [rows]
-  int32_t nz, nn;                // grid (ignored without planes)
+  int32_t nz, nn;                // grid (ignored by a summary without planes)
   const double* z_edges;         // device [nz + 1]
   const double* n_edges;         // device [nn + 1]
+};
+// the launch functions' check of the rows, and with `grid` of the bin counts
+inline bool sample_rows_ok(const SampleRowsArgs& r, bool grid = true) {
+  return r.S >= 1 && r.S <= INT32_MAX && r.levels >= 1 && r.levels <= kMaxDlas && r.ld >= r.S &&
+         (r.levels == 1 || (r.base && r.ld_base >= r.S)) &&
+         (!grid || (r.nz >= 1 && r.nn >= 1 && (int64_t)r.nz * r.nn <= kSummaryMaxBins));
+}
+
+// ---- posterior summaries (posterior_summary.hip): MAP sample and chain parameters per (row, level),
+// binned normalised masses of level 1
+struct SummaryArgs {
+  SampleRowsArgs r;
+  const double* nhi;             // [S]
   int32_t* map_ind;              // [levels][rows]
   double* map_ll;                // [levels][rows]
   double* map_z;                 // [levels][rows][kMaxDlas]
@@ -535,11 +557,11 @@ struct SummaryArgs {
 };
 hipError_t launch_posterior_summary(const SummaryArgs& a, hipStream_t s);
 
-// ---- population statistics (population.hip): the model posteriors' p_dla per spectrum, the split of
-// the level-1 masses p_dla pi_j into a Poisson plane and a short list of large probabilities, and the
+// ---- population statistics (population.hip, level_population.hip): the model posteriors per spectrum
+// (p_dla, and the posterior P_d of each DLA level), per (row, level) the binned masses and the split of
+// P_d pi_{d,j} into a Poisson plane and a short list of large probabilities with every absorber of a sample's
+// base chain counted (include/gpdla.h "Population statistics" and "... over every multi-DLA level"), and the
 // Poisson-binomial pmf of CSR trial lists
-constexpr int kPopulationMaxLarge = 8;
-constexpr int kPmfChunk = 512;           // trials per chunk polynomial
 struct ModelPosteriorArgs {
   int32_t rows, levels;
   const double* ll_null;         // [rows]
@@ -549,25 +571,28 @@ struct ModelPosteriorArgs {
   const double* lp_dla;          // [levels][ld_prior]
   const double* lp_lls;          // [rows] with ll_lls
   int64_t ld_prior;
-  double* p_dla;                 // [rows]
+  double* p_dla;                 // [rows]: launch_model_posterior
+  double* level_post;            // [levels][rows]: launch_level_posterior
 };
-struct PopulationSplitArgs {
-  int32_t rows;
-  const double* ll;              // [rows][ld], level 1, caller's sample order
-  int64_t ld, S;
-  const double* offset;          // [S]
-  const double* log_nhi;         // [S]
-  const double *zmin, *zmax;     // [rows]
-  const double* p_dla;           // [rows]
-  int32_t nz, nn;
-  const double* z_edges;         // device [nz + 1]
-  const double* n_edges;         // device [nn + 1]
+struct LevelPlanesArgs {
+  SampleRowsArgs r;
+  const double* nhi;             // [S]
+  double* planes;                // [rows][levels][kSummaryPlanes][nz nn]
+};
+// launch_level_split, and with levels = 1 launch_population_split: level_post = p_dla, ld_post = rows, and one
+// bin per entry of large_bins
+struct SplitArgs {
+  SampleRowsArgs r;
+  const double* level_post;      // [levels][ld_post]
+  int64_t ld_post;
   double p_thresh_sample, p_switch;
-  double* poisson;               // [rows][nz nn]
-  int32_t* large_inds;           // [rows][kPopulationMaxLarge], -1 = unused
+  double* poisson;               // [rows][levels][nz nn]
+  int32_t* large_inds;           // [rows][levels][kPopulationMaxLarge], -1 = unused
   double* large_probs;           // NaN = unused
-  int32_t* large_bins;           // iz nn + in, -1 = unused
+  int32_t* large_bins;           // [rows][levels][kPopulationMaxLarge][kMaxDlas] (iz nn + in), -1 = unused
 };
+using LevelSplitArgs = SplitArgs;
+using PopulationSplitArgs = SplitArgs;
 struct PmfChunkArgs {
   const double* probs;
   const int64_t* start;          // [chunks] first trial
@@ -583,56 +608,47 @@ struct PmfFoldArgs {             // the bins of more than one chunk
   double* buf[2];
 };
 hipError_t launch_model_posterior(const ModelPosteriorArgs& a, hipStream_t s);
+hipError_t launch_level_posterior(const ModelPosteriorArgs& a, hipStream_t s);
 hipError_t launch_population_split(const PopulationSplitArgs& a, hipStream_t s);
+hipError_t launch_level_planes(const LevelPlanesArgs& a, hipStream_t s);
+hipError_t launch_level_split(const LevelSplitArgs& a, hipStream_t s);
+// "<prefix><axis>_edges[i] = ...: edges must be finite and strictly increasing" for either grid kind
+int validate_grid_edges(const char* prefix, int64_t nz, int64_t nn, const double* z_edges, const double* n_edges);
 int validate_population_grid(int64_t nz, int64_t nn, const double* z_edges, const double* n_edges,
                              double p_thresh_sample, double p_switch);
 
-// ---- population statistics over every level (level_population.hip): the posterior of each DLA level,
-// and per (row, level) the binned masses and the split of P_d pi_{d,j} with every absorber of a sample's
-// base chain counted (include/gpdla.h "Population statistics over every multi-DLA level")
-struct LevelPosteriorArgs {
-  int32_t rows, levels;
-  const double* ll_null;         // [rows]
-  const double* ll_dla;          // [levels][rows]
-  const double* ll_lls;          // [rows], or nullptr: no sub-DLA model
-  const double* lp_no;           // [rows] log priors
-  const double* lp_dla;          // [levels][ld_prior]
-  const double* lp_lls;          // [rows] with ll_lls
-  int64_t ld_prior;
-  double* level_post;            // [levels][rows]
+// ---- host staging of the stand-alone entry points: one device allocation carved in 256-byte steps, freed
+// when the call returns
+struct DeviceStage {
+  char* d = nullptr;
+  size_t off = 0;
+  DeviceStage() = default;
+  DeviceStage(const DeviceStage&) = delete;
+  DeviceStage& operator=(const DeviceStage&) = delete;
+  ~DeviceStage() { if (d) (void)hipFree(d); }
+  size_t carve(size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; }
+  hipError_t alloc() { return hipMalloc((void**)&d, off ? off : 256); }
+  hipError_t upload(size_t o, const void* src, size_t bytes) { return hipMemcpy(d + o, src, bytes, hipMemcpyHostToDevice); }
+  hipError_t download(void* dst, size_t o, size_t bytes) { return hipMemcpy(dst, d + o, bytes, hipMemcpyDeviceToHost); }
+  template <class T> T* ptr(size_t o) const { return (T*)(d + o); }
 };
-struct LevelRowsArgs {           // what both level kernels read
-  int32_t rows, levels;
-  const double* ll;              // [levels][rows][ld], caller's sample order
-  int64_t ld, S;
-  const int32_t* base;           // [levels - 1][rows][ld_base] base indices, or nullptr (levels = 1)
-  int64_t ld_base;
-  const double* offset;          // [S] caller order
-  const double* log_nhi;         // [S]
-  const double* zmin;            // [rows]
-  const double* zmax;            // [rows]
-  int32_t nz, nn;
-  const double* z_edges;         // device [nz + 1]
-  const double* n_edges;         // device [nn + 1]
+// The inputs the stand-alone summary and population calls share: the rows, their base indices, the sample
+// arrays (nhi may be null), the redshift ranges and the grid's edges (nz = 0: no grid).  check() is the calls'
+// common argument check (GPDLA_EINVAL with their messages; `others` = the call's further pointers are set),
+// carve() before alloc(), upload() after it: fills r, and the device nhi.
+struct HostSampleRows {
+  const double* ll;
+  int64_t rows, S, ld;
+  const double *offset, *log_nhi, *nhi, *min_z, *max_z;
+  const int32_t* base;
+  int32_t levels;
+  int nz, nn;
+  const double *z_edges, *n_edges;
+  size_t o_ll, o_base, o_off, o_ln, o_nh, o_zmin, o_zmax, o_ed;
+  int check(bool others) const;
+  void carve(DeviceStage& st);
+  hipError_t upload(DeviceStage& st, SampleRowsArgs* r, const double** d_nhi) const;
 };
-struct LevelPlanesArgs {
-  LevelRowsArgs r;
-  const double* nhi;             // [S]
-  double* planes;                // [rows][levels][kSummaryPlanes][nz nn]
-};
-struct LevelSplitArgs {
-  LevelRowsArgs r;
-  const double* level_post;      // [levels][ld_post]
-  int64_t ld_post;
-  double p_thresh_sample, p_switch;
-  double* poisson;               // [rows][levels][nz nn]
-  int32_t* large_inds;           // [rows][levels][kPopulationMaxLarge], -1 = unused
-  double* large_probs;           // NaN = unused
-  int32_t* large_bins;           // [rows][levels][kPopulationMaxLarge][kMaxDlas], -1 = unused
-};
-hipError_t launch_level_posterior(const LevelPosteriorArgs& a, hipStream_t s);
-hipError_t launch_level_planes(const LevelPlanesArgs& a, hipStream_t s);
-hipError_t launch_level_split(const LevelSplitArgs& a, hipStream_t s);
 
 // ---- Lyman-series forest (forest.hip): rewrites the kMu / kOmega2 words of a batch's valid slots
 // between prep_kernel and the sweeps (fused fp64 layout only)

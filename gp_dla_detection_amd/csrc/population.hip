@@ -2,16 +2,11 @@
 // reference's CDDF_analysis/calc_cddf.py needs from the level-1 sample rows to put intervals on f(N),
 // dN/dX and Omega_DLA, reduced while the rows are on the device.
 //
-//   model_posterior_kernel   one thread per spectrum: the log posteriors of the 1 + D (+ 1) models and
-//                            p_dla = 1 - p_no (- p_lls), by process.py's model_posteriors* expression
-//   population_split_kernel  _split_distributions_single (calc_cddf.py:724-778) on a (z, log N_HI) grid,
-//                            one 256-thread workgroup per row.  pi_j is formed as posterior_summary.hip
-//                            forms it (the same strided partial sums and the same trees), p_j = p_dla pi_j.
-//                            The Poisson plane goes through LDS in tiles exactly like the bin planes
-//                            there: bin b belongs to thread b mod 256, which adds its samples in index
-//                            order.  The few samples with p_j >= p_switch are collected through an LDS
-//                            integer counter and then sorted by sample index, so their order does not
-//                            depend on arrival.  No floating-point atomics anywhere.
+//   model_posterior_kernel   one thread per spectrum: p_dla = 1 - p_no (- p_lls) from row_posterior.h's
+//                            model_posterior_terms, by process.py's model_posteriors* expression
+//   population_split_kernel  _split_distributions_single (calc_cddf.py:724-778) on a (z, log N_HI) grid with
+//                            p_j = p_dla pi_j, one 256-thread workgroup per row: row_posterior.h's
+//                            split_rows<1, 512, 1>, which fixes the order of operations
 //   pmf_chunk_kernel /       the Poisson-binomial pmf of each bin of a CSR list: the coefficients of
 //   pmf_fold_kernel          prod_j (1 - p_j + p_j x).  A bin is cut into chunks of kPmfChunk trials in
 //                            list order; one workgroup per chunk runs pmf[k] <- pmf[k] (1 - p) + pmf[k-1] p
@@ -27,191 +22,27 @@
 
 #include "../../include/gpdla.h"
 #include "internal.h"
-#include "sample_bins.h"
+#include "row_posterior.h"
 
 namespace gpdla {
 namespace {
 
-constexpr int kPopThreads = 256;
-constexpr int kPopWaves = kPopThreads / 64;
-constexpr int kPopTile = 512;        // samples staged per pass (12 B each)
-constexpr int kPopCandidates = 16;   // LDS slots for p_j >= p_switch; the kPopulationMaxLarge lowest indices are kept
-
 static_assert(kPopulationMaxLarge == GPDLA_POPULATION_MAX_LARGE, "gpdla.h");
 static_assert(kPmfChunk == GPDLA_PMF_CHUNK, "gpdla.h");
-static_assert(kPopTile % 4 == 0, "the scan reads four bin indices at a time");
 
-__host__ __device__ inline size_t pop_up16(size_t x) { return (x + 15) & ~(size_t)15; }
-struct PopLds {
-  size_t red_v, red_i, edges_z, edges_n, plane, p, bin, cand_i, cand_p, cand_b, count, total;
-};
-__host__ __device__ inline PopLds pop_lds(int nz, int nn) {
-  PopLds l{};
-  size_t o = 0;
-  l.red_v = o; o = pop_up16(o + kPopWaves * 8);
-  l.red_i = o; o = pop_up16(o + kPopWaves * 4);
-  l.edges_z = o; o = pop_up16(o + (size_t)(nz + 1) * 8);
-  l.edges_n = o; o = pop_up16(o + (size_t)(nn + 1) * 8);
-  l.plane = o; o = pop_up16(o + (size_t)nz * nn * 8);
-  l.p = o; o = pop_up16(o + (size_t)kPopTile * 8);
-  l.bin = o; o = pop_up16(o + (size_t)kPopTile * 4);
-  l.cand_p = o; o = pop_up16(o + (size_t)kPopCandidates * 8);
-  l.cand_i = o; o = pop_up16(o + (size_t)kPopCandidates * 4);
-  l.cand_b = o; o = pop_up16(o + (size_t)kPopCandidates * 4);
-  l.count = o; o = pop_up16(o + 4);
-  l.total = o;
-  return l;
-}
-
-__global__ __launch_bounds__(kPopThreads) void population_split_kernel(PopulationSplitArgs a) {
+__global__ __launch_bounds__(kRowThreads) void population_split_kernel(PopulationSplitArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int row = blockIdx.x, tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const PopLds L = pop_lds(a.nz, a.nn);
-  double* s_rv = (double*)(smem + L.red_v);
-  int32_t* s_ri = (int32_t*)(smem + L.red_i);
-  const int32_t S = (int32_t)a.S;
-  const double* ll = a.ll + (int64_t)row * a.ld;
-
-  // ---- the maximum over the non-NaN entries (posterior_summary.hip's MAP reduction)
-  double bv = 0.0;
-  int32_t bi = -1;
-  for (int64_t j = tid; j < S; j += kPopThreads) {
-    const double v = ll[j];
-    if (v == v && (bi < 0 || v > bv)) { bv = v; bi = (int32_t)j; }
-  }
-  auto merge = [](double& v, int32_t& i, double ov, int32_t oi) {
-    if (oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i))) { v = ov; i = oi; }
-  };
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(bv, o);
-    const int32_t oi = __shfl_xor(bi, o);
-    merge(bv, bi, ov, oi);
-  }
-  if (lane == 0) { s_rv[wave] = bv; s_ri[wave] = bi; }
-  __syncthreads();
-  bv = s_rv[0]; bi = s_ri[0];
-#pragma unroll
-  for (int w = 1; w < kPopWaves; ++w) merge(bv, bi, s_rv[w], s_ri[w]);
-  __syncthreads();
-
-  // ---- W = sum_j exp(l_j - max), NaN -> 0: the same partial sums and trees as the bin planes' W
-  const double m = bv;
-  double loc = 0.0;
-  for (int64_t j = tid; j < S; j += kPopThreads) {
-    const double v = ll[j];
-    loc += (v == v) ? exp(v - m) : 0.0;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) loc += __shfl_xor(loc, o);
-  if (lane == 0) s_rv[wave] = loc;
-  __syncthreads();
-  double W = s_rv[0];
-#pragma unroll
-  for (int w = 1; w < kPopWaves; ++w) W += s_rv[w];
-  const bool usable = W > 0.0 && W < INFINITY;
-
-  double* s_ez = (double*)(smem + L.edges_z);
-  double* s_en = (double*)(smem + L.edges_n);
-  double* s_pl = (double*)(smem + L.plane);
-  double* s_p = (double*)(smem + L.p);
-  int32_t* s_bin = (int32_t*)(smem + L.bin);
-  double* s_cp = (double*)(smem + L.cand_p);
-  int32_t* s_ci = (int32_t*)(smem + L.cand_i);
-  int32_t* s_cb = (int32_t*)(smem + L.cand_b);
-  int32_t* s_cnt = (int32_t*)(smem + L.count);
-  const int nb = a.nz * a.nn;
-  for (int i = tid; i <= a.nz; i += kPopThreads) s_ez[i] = a.z_edges[i];
-  for (int i = tid; i <= a.nn; i += kPopThreads) s_en[i] = a.n_edges[i];
-  for (int i = tid; i < nb; i += kPopThreads) s_pl[i] = 0.0;
-  if (tid == 0) *s_cnt = 0;
-  const double zmin = a.zmin[row], zmax = a.zmax[row], p_dla = a.p_dla[row];
-  for (int64_t t0 = 0; t0 < S; t0 += kPopTile) {
-    __syncthreads();   // edges, zeroed plane and counter ready; the previous tile's scan is over
-    for (int i = tid; i < kPopTile; i += kPopThreads) {
-      const int64_t j = t0 + i;
-      int32_t b = -1;
-      double p = 0.0;
-      if (j < S) {
-        const double v = ll[j];
-        const double w = (v == v) ? exp(v - m) : 0.0;
-        const double pi = usable ? w / W : 0.0;
-        p = p_dla * pi;
-        const int iz = find_bin(s_ez, a.nz, sample_z(zmin, zmax, a.offset[j]));
-        const int in = find_bin(s_en, a.nn, a.log_nhi[j]);
-        if (iz >= 0 && in >= 0) b = iz * a.nn + in;
-        if (b >= 0 && p >= a.p_switch) {          // kept exactly; never enters the Poisson plane
-          const int slot = atomicAdd(s_cnt, 1);   // integer, LDS: the order is fixed by the sort below
-          if (slot < kPopCandidates) { s_cp[slot] = p; s_ci[slot] = (int32_t)j; s_cb[slot] = b; }
-          b = -1;
-        } else if (!(p > a.p_thresh_sample && p < a.p_switch)) {
-          b = -1;                                 // below the sample threshold, or NaN
-        }
-      }
-      s_p[i] = p; s_bin[i] = b;
-    }
-    __syncthreads();
-    const int cnt = (int)min((int64_t)kPopTile, S - t0);
-    for (int i0 = 0; i0 < cnt; i0 += 4) {
-      const int4 b4 = *(const int4*)(s_bin + i0);   // the same address in every lane: a broadcast
-      const int bs[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int b = bs[u];
-        if (b >= 0 && (b & (kPopThreads - 1)) == tid) s_pl[b] += s_p[i0 + u];
-      }
-    }
-  }
-  __syncthreads();
-  double* out = a.poisson + (int64_t)row * nb;
-  for (int i = tid; i < nb; i += kPopThreads) out[i] = s_pl[i];
-  if (tid == 0) {
-    // sum pi = 1 bounds the candidates by 1 / p_switch <= kPopulationMaxLarge; were there ever more, the
-    // lowest sample indices among the first kPopCandidates arrivals are kept
-    const int n = min(*s_cnt, kPopCandidates);
-    for (int i = 1; i < n; ++i) {      // insertion sort by sample index
-      const int32_t ci = s_ci[i], cb = s_cb[i];
-      const double cp = s_cp[i];
-      int k = i - 1;
-      while (k >= 0 && s_ci[k] > ci) { s_ci[k + 1] = s_ci[k]; s_cb[k + 1] = s_cb[k]; s_cp[k + 1] = s_cp[k]; --k; }
-      s_ci[k + 1] = ci; s_cb[k + 1] = cb; s_cp[k + 1] = cp;
-    }
-    const int64_t o = (int64_t)row * kPopulationMaxLarge;
-    for (int i = 0; i < kPopulationMaxLarge; ++i) {
-      const bool use = i < n;
-      a.large_inds[o + i] = use ? s_ci[i] : -1;
-      a.large_probs[o + i] = use ? s_cp[i] : NAN;
-      a.large_bins[o + i] = use ? s_cb[i] : -1;
-    }
-  }
+  const int row = blockIdx.x;
+  split_rows<1, kRowTileOne, 1>(a, row, row, a.level_post[row], split_lds(a.r.nz, a.r.nn, kRowTileOne, 1, 1), smem);
 }
 
-// process.py model_posteriors / model_posteriors_multi / model_posteriors_sub for one spectrum: columns
-// no-DLA, DLA levels 1..D, then (sub) the sub-DLA model; a NaN evidence at a level >= 2 enters as -inf,
-// any other NaN makes every posterior NaN (numpy's max and sum propagate it)
-__global__ __launch_bounds__(kPopThreads) void model_posterior_kernel(ModelPosteriorArgs a) {
+__global__ __launch_bounds__(kRowThreads) void model_posterior_kernel(ModelPosteriorArgs a) {
 #pragma clang fp contract(off)
-  const int q = blockIdx.x * kPopThreads + threadIdx.x;
+  const int q = blockIdx.x * kRowThreads + threadIdx.x;
   if (q >= a.rows) return;
-  double lp[kMaxDlas + 2];
-  int n = 0;
-  lp[n++] = a.lp_no[q] + a.ll_null[q];
-  for (int d = 0; d < a.levels; ++d) {
-    double v = a.lp_dla[(int64_t)d * a.ld_prior + q] + a.ll_dla[(int64_t)d * a.rows + q];
-    if (d >= 1 && v != v) v = -INFINITY;
-    lp[n++] = v;
-  }
-  if (a.ll_lls) lp[n++] = a.lp_lls[q] + a.ll_lls[q];
-  double mx = lp[0];
-  bool nan = mx != mx;
-  for (int i = 1; i < n; ++i) {
-    nan = nan || lp[i] != lp[i];
-    if (lp[i] > mx) mx = lp[i];
-  }
-  if (nan) { a.p_dla[q] = NAN; return; }
-  double e[kMaxDlas + 2], sum = 0.0;
-  for (int i = 0; i < n; ++i) { e[i] = exp(lp[i] - mx); sum += e[i]; }
+  double e[kMaxDlas + 2], sum;
+  int n;
+  if (!model_posterior_terms(a, q, e, sum, n)) { a.p_dla[q] = NAN; return; }
   const double p_no = e[0] / sum;
   double p = 1.0 - p_no;
   if (a.ll_lls) p = p - e[n - 1] / sum;
@@ -220,21 +51,21 @@ __global__ __launch_bounds__(kPopThreads) void model_posterior_kernel(ModelPoste
 
 // ---- Poisson-binomial pmf ----------------------------------------------------------------------
 // chunk c: trials probs[start .. start + len) of its bin -> len + 1 coefficients at out
-__global__ __launch_bounds__(kPopThreads) void pmf_chunk_kernel(PmfChunkArgs a) {
+__global__ __launch_bounds__(kRowThreads) void pmf_chunk_kernel(PmfChunkArgs a) {
   __shared__ double s_p[kPmfChunk];
   __shared__ double s_c[2][kPmfChunk + 2];
   const int c = blockIdx.x, tid = threadIdx.x;
   const int len = a.len[c];
   const double* p = a.probs + a.start[c];
-  for (int i = tid; i < len; i += kPopThreads) s_p[i] = p[i];
-  for (int i = tid; i <= kPmfChunk; i += kPopThreads) { s_c[0][i] = i == 0 ? 1.0 : 0.0; s_c[1][i] = 0.0; }
+  for (int i = tid; i < len; i += kRowThreads) s_p[i] = p[i];
+  for (int i = tid; i <= kPmfChunk; i += kRowThreads) { s_c[0][i] = i == 0 ? 1.0 : 0.0; s_c[1][i] = 0.0; }
   __syncthreads();
   int cur = 0;
   for (int j = 0; j < len; ++j) {
     const double pj = s_p[j], qj = 1.0 - pj;
     const double* src = s_c[cur];
     double* dst = s_c[cur ^ 1];
-    for (int k = tid; k <= j + 1; k += kPopThreads) {
+    for (int k = tid; k <= j + 1; k += kRowThreads) {
       const double keep = src[k] * qj;                         // src[j + 1] is still 0
       dst[k] = k > 0 ? __builtin_fma(src[k - 1], pj, keep) : keep;
     }
@@ -242,29 +73,29 @@ __global__ __launch_bounds__(kPopThreads) void pmf_chunk_kernel(PmfChunkArgs a) 
     cur ^= 1;
   }
   double* out = a.dst[c];
-  for (int i = tid; i <= len; i += kPopThreads) out[i] = s_c[cur][i];
+  for (int i = tid; i <= len; i += kRowThreads) out[i] = s_c[cur][i];
 }
 
 // fold step s of every bin with more than s chunks: next[k] = sum_i P[i] cur[k - i], i ascending, where cur
 // holds the product of chunks 0 .. s - 1 (lr + 1 coefficients) and P is chunk s (lp + 1 coefficients)
-__global__ __launch_bounds__(kPopThreads) void pmf_fold_kernel(PmfFoldArgs a, int step) {
+__global__ __launch_bounds__(kRowThreads) void pmf_fold_kernel(PmfFoldArgs a, int step) {
   __shared__ double s_P[kPmfChunk + 1];
-  __shared__ double s_R[kPmfChunk + kPopThreads];
+  __shared__ double s_R[kPmfChunk + kRowThreads];
   const int b = blockIdx.y, tid = threadIdx.x;
   const int nch = a.nch[b];
   if (nch <= step) return;
   const int64_t n = a.n[b];
   const int64_t lr = (int64_t)step * kPmfChunk;
   const int lp = (int)min((int64_t)kPmfChunk, n - lr);
-  const int64_t k0 = (int64_t)blockIdx.x * kPopThreads;
+  const int64_t k0 = (int64_t)blockIdx.x * kRowThreads;
   if (k0 > lr + lp) return;
   // the bin ends in buffer 0 after its last step: step s reads buffer (nch - s) & 1
   const double* cur = a.buf[(nch - step) & 1] + a.out_off[b];
   double* next = a.buf[(nch - step - 1) & 1] + a.out_off[b];
   const double* P = a.chunks + a.chunk_off[b] + lr + step;     // chunk c starts c kPmfChunk + c entries in
-  for (int i = tid; i <= lp; i += kPopThreads) s_P[i] = P[i];
+  for (int i = tid; i <= lp; i += kRowThreads) s_P[i] = P[i];
   const int64_t w0 = k0 - lp;                                  // the window cur[w0 .. k0 + 255]
-  for (int i = tid; i < lp + kPopThreads; i += kPopThreads) {
+  for (int i = tid; i < lp + kRowThreads; i += kRowThreads) {
     const int64_t r = w0 + i;
     s_R[i] = (r >= 0 && r <= lr) ? cur[r] : 0.0;
   }
@@ -280,20 +111,31 @@ __global__ __launch_bounds__(kPopThreads) void pmf_fold_kernel(PmfFoldArgs a, in
 }  // namespace
 
 hipError_t launch_population_split(const PopulationSplitArgs& a, hipStream_t s) {
-  if (a.rows < 1) return hipSuccess;
-  if (a.S < 1 || a.S > INT32_MAX || a.nz < 1 || a.nn < 1 || (int64_t)a.nz * a.nn > kSummaryMaxBins)
-    return hipErrorInvalidValue;
-  const PopLds L = pop_lds(a.nz, a.nn);
-  hipLaunchKernelGGL(population_split_kernel, dim3((unsigned)a.rows), dim3(kPopThreads), L.total, s, a);
+  if (a.r.rows < 1) return hipSuccess;
+  if (!sample_rows_ok(a.r) || a.r.levels != 1) return hipErrorInvalidValue;
+  const RowLds L = split_lds(a.r.nz, a.r.nn, kRowTileOne, 1, 1);
+  hipLaunchKernelGGL(population_split_kernel, dim3((unsigned)a.r.rows), dim3(kRowThreads), L.total, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_model_posterior(const ModelPosteriorArgs& a, hipStream_t s) {
   if (a.rows < 1) return hipSuccess;
   if (a.levels < 1 || a.levels > kMaxDlas) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(model_posterior_kernel, dim3((unsigned)((a.rows + kPopThreads - 1) / kPopThreads)), dim3(kPopThreads),
+  hipLaunchKernelGGL(model_posterior_kernel, dim3((unsigned)((a.rows + kRowThreads - 1) / kRowThreads)), dim3(kRowThreads),
                      0, s, a);
   return hipGetLastError();
+}
+
+int validate_grid_edges(const char* prefix, int64_t nz, int64_t nn, const double* z_edges, const double* n_edges) {
+  for (int ax = 0; ax < 2; ++ax) {
+    const double* ed = ax ? n_edges : z_edges;
+    const int64_t n = ax ? nn : nz;
+    for (int64_t i = 0; i <= n; ++i)
+      if (!std::isfinite(ed[i]) || (i > 0 && !(ed[i] > ed[i - 1])))
+        return set_error(GPDLA_EINVAL, "%s%s[%lld] = %g: edges must be finite and strictly increasing", prefix,
+                         ax ? "log_nhi_edges" : "z_edges", (long long)i, ed[i]);
+  }
+  return GPDLA_OK;
 }
 
 // the thresholds and the grid of a population call (shared with engine.hip)
@@ -305,20 +147,48 @@ int validate_population_grid(int64_t nz, int64_t nn, const double* z_edges, cons
     return set_error(GPDLA_EINVAL, "population grid %lld x %lld exceeds %d bins", (long long)nz, (long long)nn,
                      GPDLA_SUMMARY_MAX_BINS);
   if (!z_edges || !n_edges) return set_error(GPDLA_EINVAL, "null population edge array");
-  for (int ax = 0; ax < 2; ++ax) {
-    const double* ed = ax ? n_edges : z_edges;
-    const int64_t n = ax ? nn : nz;
-    for (int64_t i = 0; i <= n; ++i)
-      if (!std::isfinite(ed[i]) || (i > 0 && !(ed[i] > ed[i - 1])))
-        return set_error(GPDLA_EINVAL, "population %s[%lld] = %g: edges must be finite and strictly increasing",
-                         ax ? "log_nhi_edges" : "z_edges", (long long)i, ed[i]);
-  }
+  if (int rc = validate_grid_edges("population ", nz, nn, z_edges, n_edges)) return rc;
   if (!(p_switch >= 1.0 / GPDLA_POPULATION_MAX_LARGE && p_switch < INFINITY))
     return set_error(GPDLA_EINVAL, "p_switch = %g: must be finite and >= 1/%d (the large list has %d slots)", p_switch,
                      GPDLA_POPULATION_MAX_LARGE, GPDLA_POPULATION_MAX_LARGE);
   if (!(p_thresh_sample >= 0.0 && p_thresh_sample < p_switch))
     return set_error(GPDLA_EINVAL, "p_thresh_sample = %g outside [0, p_switch = %g)", p_thresh_sample, p_switch);
   return GPDLA_OK;
+}
+
+int HostSampleRows::check(bool others) const {
+  if (!ll || !offset || !log_nhi || !min_z || !max_z || !others) return set_error(GPDLA_EINVAL, "null argument");
+  if (rows < 0 || S < 1 || ld < S || rows > INT32_MAX || S > INT32_MAX)
+    return set_error(GPDLA_EINVAL, "rows=%lld S=%lld ld=%lld", (long long)rows, (long long)S, (long long)ld);
+  if (levels < 1 || levels > GPDLA_MAX_DLAS) return set_error(GPDLA_EINVAL, "levels=%d outside 1..%d", levels, GPDLA_MAX_DLAS);
+  if (levels > 1 && !base) return set_error(GPDLA_EINVAL, "levels=%d needs base_inds", levels);
+  return GPDLA_OK;
+}
+
+void HostSampleRows::carve(DeviceStage& st) {
+  const size_t R = (size_t)rows, LV = (size_t)levels;
+  o_ll = st.carve(LV * R * ld * 8); o_base = st.carve((LV - 1) * R * ld * 4);
+  o_off = st.carve((size_t)S * 8); o_ln = st.carve((size_t)S * 8); o_nh = st.carve(nhi ? (size_t)S * 8 : 0);
+  o_zmin = st.carve(R * 8); o_zmax = st.carve(R * 8); o_ed = st.carve((size_t)(nz + nn + 2) * 8);
+}
+
+hipError_t HostSampleRows::upload(DeviceStage& st, SampleRowsArgs* r, const double** d_nhi) const {
+  const size_t R = (size_t)rows, LV = (size_t)levels;
+  const struct { size_t o; const void* src; size_t bytes; } copies[] = {
+      {o_ll, ll, LV * R * ld * 8}, {o_base, base, (LV - 1) * R * ld * 4}, {o_off, offset, (size_t)S * 8},
+      {o_ln, log_nhi, (size_t)S * 8}, {o_nh, nhi, nhi ? (size_t)S * 8 : 0}, {o_zmin, min_z, R * 8}, {o_zmax, max_z, R * 8},
+      {o_ed, z_edges, nz ? (size_t)(nz + 1) * 8 : 0}, {o_ed + (size_t)(nz + 1) * 8, n_edges, nz ? (size_t)(nn + 1) * 8 : 0}};
+  for (const auto& c : copies)
+    if (c.bytes)
+      if (hipError_t e = st.upload(c.o, c.src, c.bytes)) return e;
+  *r = SampleRowsArgs{};
+  r->rows = (int32_t)rows; r->levels = levels; r->ll = st.ptr<const double>(o_ll); r->ld = ld; r->S = S;
+  r->base = levels > 1 ? st.ptr<const int32_t>(o_base) : nullptr; r->ld_base = ld;
+  r->offset = st.ptr<const double>(o_off); r->log_nhi = st.ptr<const double>(o_ln);
+  r->zmin = st.ptr<const double>(o_zmin); r->zmax = st.ptr<const double>(o_zmax);
+  r->nz = nz; r->nn = nn; r->z_edges = st.ptr<const double>(o_ed); r->n_edges = st.ptr<const double>(o_ed) + nz + 1;
+  if (d_nhi) *d_nhi = st.ptr<const double>(o_nh);
+  return hipSuccess;
 }
 
 }  // namespace gpdla
@@ -331,62 +201,38 @@ int gpdla_population_split_f64(int32_t device, const double* ll, int64_t rows, i
                                const double* offset_samples, const double* log_nhi_samples, const double* min_z,
                                const double* max_z, const double* p_dlas, const gpdla_population_spec* spec,
                                double* poisson_plane, int32_t* large_inds, double* large_probs, int32_t* large_bins) {
-  if (!ll || !offset_samples || !log_nhi_samples || !min_z || !max_z || !p_dlas || !spec || !poisson_plane ||
-      !large_inds || !large_probs || !large_bins)
-    return set_error(GPDLA_EINVAL, "null argument");
-  if (rows < 0 || S < 1 || ld < S || rows > INT32_MAX || S > INT32_MAX)
-    return set_error(GPDLA_EINVAL, "rows=%lld S=%lld ld=%lld", (long long)rows, (long long)S, (long long)ld);
-  int rc = validate_population_grid(spec->num_z_bins, spec->num_nhi_bins, spec->z_edges, spec->log_nhi_edges,
-                                    spec->p_thresh_sample, spec->p_switch);
+  HostSampleRows h{ll, rows, S, ld, offset_samples, log_nhi_samples, nullptr, min_z, max_z, nullptr, 1};
+  int rc = h.check(p_dlas && spec && poisson_plane && large_inds && large_probs && large_bins);
   if (rc) return rc;
+  if ((rc = validate_population_grid(spec->num_z_bins, spec->num_nhi_bins, spec->z_edges, spec->log_nhi_edges,
+                                     spec->p_thresh_sample, spec->p_switch)))
+    return rc;
   for (int64_t q = 0; q < rows; ++q)
     if (p_dlas[q] == p_dlas[q] && !(p_dlas[q] >= 0.0 && p_dlas[q] <= 1.0))
       return set_error(GPDLA_EINVAL, "p_dlas[%lld] = %g outside [0, 1]", (long long)q, p_dlas[q]);
   if ((rc = check_device(device))) return rc;
   if (rows == 0) return GPDLA_OK;
   HIP_TRY(hipSetDevice(device));
-  const int nz = spec->num_z_bins, nn = spec->num_nhi_bins;
-  const size_t R = (size_t)rows, nbins = (size_t)nz * nn, NL = GPDLA_POPULATION_MAX_LARGE;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_ll = carve(R * ld * 8), o_off = carve((size_t)S * 8), o_ln = carve((size_t)S * 8);
-  const size_t o_zmin = carve(R * 8), o_zmax = carve(R * 8), o_p = carve(R * 8), o_ed = carve((size_t)(nz + nn + 2) * 8);
-  const size_t o_pl = carve(R * nbins * 8), o_li = carve(R * NL * 4), o_lp = carve(R * NL * 8), o_lb = carve(R * NL * 4);
-  char* d = nullptr;
-  auto done = [&](int code) {
-    if (d) (void)hipFree(d);
-    return code;
-  };
-#define TRY_P(expr)                                                                                                     \
-  do {                                                                                                                  \
-    hipError_t e_ = (expr);                                                                                             \
-    if (e_ != hipSuccess)                                                                                               \
-      return done(set_error(e_ == hipErrorOutOfMemory ? GPDLA_ENOMEM : GPDLA_EDEVICE, "population: %s failed: %s", #expr, \
-                            hipGetErrorString(e_)));                                                                    \
-  } while (0)
-  TRY_P(hipMalloc((void**)&d, off));
-  TRY_P(hipMemcpy(d + o_ll, ll, R * ld * 8, hipMemcpyHostToDevice));
-  TRY_P(hipMemcpy(d + o_off, offset_samples, (size_t)S * 8, hipMemcpyHostToDevice));
-  TRY_P(hipMemcpy(d + o_ln, log_nhi_samples, (size_t)S * 8, hipMemcpyHostToDevice));
-  TRY_P(hipMemcpy(d + o_zmin, min_z, R * 8, hipMemcpyHostToDevice));
-  TRY_P(hipMemcpy(d + o_zmax, max_z, R * 8, hipMemcpyHostToDevice));
-  TRY_P(hipMemcpy(d + o_p, p_dlas, R * 8, hipMemcpyHostToDevice));
-  TRY_P(hipMemcpy(d + o_ed, spec->z_edges, (size_t)(nz + 1) * 8, hipMemcpyHostToDevice));
-  TRY_P(hipMemcpy(d + o_ed + (size_t)(nz + 1) * 8, spec->log_nhi_edges, (size_t)(nn + 1) * 8, hipMemcpyHostToDevice));
+  h.nz = spec->num_z_bins; h.nn = spec->num_nhi_bins; h.z_edges = spec->z_edges; h.n_edges = spec->log_nhi_edges;
+  const size_t R = (size_t)rows, nbins = (size_t)h.nz * h.nn, NL = GPDLA_POPULATION_MAX_LARGE;
+  DeviceStage st;
+  h.carve(st);
+  const size_t o_p = st.carve(R * 8), o_pl = st.carve(R * nbins * 8), o_li = st.carve(R * NL * 4);
+  const size_t o_lp = st.carve(R * NL * 8), o_lb = st.carve(R * NL * 4);
   PopulationSplitArgs pa{};
-  pa.rows = (int32_t)rows; pa.ll = (const double*)(d + o_ll); pa.ld = ld; pa.S = S;
-  pa.offset = (const double*)(d + o_off); pa.log_nhi = (const double*)(d + o_ln);
-  pa.zmin = (const double*)(d + o_zmin); pa.zmax = (const double*)(d + o_zmax); pa.p_dla = (const double*)(d + o_p);
-  pa.nz = nz; pa.nn = nn; pa.z_edges = (const double*)(d + o_ed); pa.n_edges = (const double*)(d + o_ed) + nz + 1;
+  HIP_TRY_IN("population", st.alloc());
+  HIP_TRY_IN("population", h.upload(st, &pa.r, nullptr));
+  HIP_TRY_IN("population", st.upload(o_p, p_dlas, R * 8));
+  pa.level_post = st.ptr<const double>(o_p); pa.ld_post = rows;
   pa.p_thresh_sample = spec->p_thresh_sample; pa.p_switch = spec->p_switch;
-  pa.poisson = (double*)(d + o_pl); pa.large_inds = (int32_t*)(d + o_li); pa.large_probs = (double*)(d + o_lp);
-  pa.large_bins = (int32_t*)(d + o_lb);
-  TRY_P(launch_population_split(pa, nullptr));
-  TRY_P(hipMemcpy(poisson_plane, d + o_pl, R * nbins * 8, hipMemcpyDeviceToHost));
-  TRY_P(hipMemcpy(large_inds, d + o_li, R * NL * 4, hipMemcpyDeviceToHost));
-  TRY_P(hipMemcpy(large_probs, d + o_lp, R * NL * 8, hipMemcpyDeviceToHost));
-  TRY_P(hipMemcpy(large_bins, d + o_lb, R * NL * 4, hipMemcpyDeviceToHost));
-  return done(GPDLA_OK);
+  pa.poisson = st.ptr<double>(o_pl); pa.large_inds = st.ptr<int32_t>(o_li); pa.large_probs = st.ptr<double>(o_lp);
+  pa.large_bins = st.ptr<int32_t>(o_lb);
+  HIP_TRY_IN("population", launch_population_split(pa, nullptr));
+  HIP_TRY_IN("population", st.download(poisson_plane, o_pl, R * nbins * 8));
+  HIP_TRY_IN("population", st.download(large_inds, o_li, R * NL * 4));
+  HIP_TRY_IN("population", st.download(large_probs, o_lp, R * NL * 8));
+  HIP_TRY_IN("population", st.download(large_bins, o_lb, R * NL * 4));
+  return GPDLA_OK;
 }
 
 int gpdla_poisson_binomial_pmf_f64(int32_t device, const double* probs, const int64_t* offsets, int64_t num_bins,
@@ -435,19 +281,14 @@ int gpdla_poisson_binomial_pmf_f64(int32_t device, const double* probs, const in
   }
   const size_t NC = c_len.size(), NF = f_n.size();
   if (NF > 65535) return set_error(GPDLA_EINVAL, "%lld bins beyond %d trials in one call (at most 65535)", (long long)NF, kPmfChunk);
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_probs = carve((size_t)total * 8), o_buf0 = carve(out_total * 8), o_buf1 = carve(NF ? out_total * 8 : 0);
-  const size_t o_chunks = carve((size_t)chunk_entries * 8), o_cs = carve(NC * 8), o_cl = carve(NC * 4), o_cd = carve(NC * 8);
-  const size_t o_fn = carve(NF * 8), o_fo = carve(NF * 8), o_fc = carve(NF * 8), o_fh = carve(NF * 4);
-  char* d = nullptr;
-  auto done = [&](int code) {
-    if (d) (void)hipFree(d);
-    return code;
-  };
-  TRY_P(hipMalloc((void**)&d, std::max<size_t>(off, 256)));
-  double* bufs[2] = {(double*)(d + o_buf0), (double*)(d + o_buf1)};
-  double* chunks = (double*)(d + o_chunks);
+  DeviceStage st;
+  const size_t o_probs = st.carve((size_t)total * 8), o_buf0 = st.carve(out_total * 8), o_buf1 = st.carve(NF ? out_total * 8 : 0);
+  const size_t o_chunks = st.carve((size_t)chunk_entries * 8), o_cs = st.carve(NC * 8), o_cl = st.carve(NC * 4);
+  const size_t o_cd = st.carve(NC * 8), o_fn = st.carve(NF * 8), o_fo = st.carve(NF * 8), o_fc = st.carve(NF * 8);
+  const size_t o_fh = st.carve(NF * 4);
+  HIP_TRY_IN("population", st.alloc());
+  double* bufs[2] = {st.ptr<double>(o_buf0), st.ptr<double>(o_buf1)};
+  double* chunks = st.ptr<double>(o_chunks);
   // where each chunk's polynomial goes: a single-chunk bin's straight to the output; chunk 0 of a longer
   // bin to the buffer its fold starts from; the others to the chunk store
   std::vector<double*> c_dst(NC);
@@ -463,38 +304,37 @@ int gpdla_poisson_binomial_pmf_f64(int32_t device, const double* probs, const in
       if (c_local[c] == nch - 1) ++f;
     }
   }
-  if (total) TRY_P(hipMemcpy(d + o_probs, probs, (size_t)total * 8, hipMemcpyHostToDevice));
-  TRY_P(hipMemcpy(d + o_cs, c_start.data(), NC * 8, hipMemcpyHostToDevice));
-  TRY_P(hipMemcpy(d + o_cl, c_len.data(), NC * 4, hipMemcpyHostToDevice));
-  TRY_P(hipMemcpy(d + o_cd, c_dst.data(), NC * 8, hipMemcpyHostToDevice));
+  if (total) HIP_TRY_IN("population", st.upload(o_probs, probs, (size_t)total * 8));
+  HIP_TRY_IN("population", st.upload(o_cs, c_start.data(), NC * 8));
+  HIP_TRY_IN("population", st.upload(o_cl, c_len.data(), NC * 4));
+  HIP_TRY_IN("population", st.upload(o_cd, c_dst.data(), NC * 8));
   PmfChunkArgs ca{};
-  ca.probs = (const double*)(d + o_probs); ca.start = (const int64_t*)(d + o_cs); ca.len = (const int32_t*)(d + o_cl);
-  ca.dst = (double* const*)(d + o_cd);
+  ca.probs = st.ptr<const double>(o_probs); ca.start = st.ptr<const int64_t>(o_cs); ca.len = st.ptr<const int32_t>(o_cl);
+  ca.dst = st.ptr<double* const>(o_cd);
   lt.before();
-  hipLaunchKernelGGL(pmf_chunk_kernel, dim3((unsigned)NC), dim3(kPopThreads), 0, nullptr, ca);
-  TRY_P(hipGetLastError());
+  hipLaunchKernelGGL(pmf_chunk_kernel, dim3((unsigned)NC), dim3(kRowThreads), 0, nullptr, ca);
+  HIP_TRY_IN("population", hipGetLastError());
   lt.after();
   if (NF) {
-    TRY_P(hipMemcpy(d + o_fn, f_n.data(), NF * 8, hipMemcpyHostToDevice));
-    TRY_P(hipMemcpy(d + o_fo, f_out.data(), NF * 8, hipMemcpyHostToDevice));
-    TRY_P(hipMemcpy(d + o_fc, f_chunk.data(), NF * 8, hipMemcpyHostToDevice));
-    TRY_P(hipMemcpy(d + o_fh, f_nch.data(), NF * 4, hipMemcpyHostToDevice));
+    HIP_TRY_IN("population", st.upload(o_fn, f_n.data(), NF * 8));
+    HIP_TRY_IN("population", st.upload(o_fo, f_out.data(), NF * 8));
+    HIP_TRY_IN("population", st.upload(o_fc, f_chunk.data(), NF * 8));
+    HIP_TRY_IN("population", st.upload(o_fh, f_nch.data(), NF * 4));
     PmfFoldArgs fa{};
-    fa.n = (const int64_t*)(d + o_fn); fa.out_off = (const int64_t*)(d + o_fo); fa.chunk_off = (const int64_t*)(d + o_fc);
-    fa.nch = (const int32_t*)(d + o_fh); fa.chunks = chunks; fa.buf[0] = bufs[0]; fa.buf[1] = bufs[1];
+    fa.n = st.ptr<const int64_t>(o_fn); fa.out_off = st.ptr<const int64_t>(o_fo); fa.chunk_off = st.ptr<const int64_t>(o_fc);
+    fa.nch = st.ptr<const int32_t>(o_fh); fa.chunks = chunks; fa.buf[0] = bufs[0]; fa.buf[1] = bufs[1];
     lt.before();
     for (int s = 1; s < max_nch; ++s) {
       const int64_t len = std::min<int64_t>(max_n, (int64_t)(s + 1) * kPmfChunk) + 1;
-      hipLaunchKernelGGL(pmf_fold_kernel, dim3((unsigned)((len + kPopThreads - 1) / kPopThreads), (unsigned)NF),
-                         dim3(kPopThreads), 0, nullptr, fa, s);
-      TRY_P(hipGetLastError());
+      hipLaunchKernelGGL(pmf_fold_kernel, dim3((unsigned)((len + kRowThreads - 1) / kRowThreads), (unsigned)NF),
+                         dim3(kRowThreads), 0, nullptr, fa, s);
+      HIP_TRY_IN("population", hipGetLastError());
     }
     lt.after();
   }
-  TRY_P(hipMemcpy(pmf, bufs[0], out_total * 8, hipMemcpyDeviceToHost));
+  HIP_TRY_IN("population", st.download(pmf, o_buf0, out_total * 8));
   lt.finish();
-#undef TRY_P
-  return done(GPDLA_OK);
+  return GPDLA_OK;
 }
 
 }  // extern "C"

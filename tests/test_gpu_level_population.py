@@ -129,10 +129,13 @@ def test_exact_cases_on_the_device(D):
 
 
 # ------------------------------------------------------------------- 3. reduction to what exists, bitwise
-@pytest.mark.parametrize("S", [4, 257, 1025])
-def test_level_one_is_the_existing_kernels(S):
+@pytest.mark.parametrize("S,grid", [pytest.param(S, grid, id=str(S) if grid == "7x5" else f"{S}-{grid}")
+                                    for grid in ("7x5", "32x32") for S in (4, 255, 256, 257, 511, 512, 513, 1025)])
+def test_level_one_is_the_existing_kernels(S, grid):
+    """The level-1 and the level kernels are one body (csrc/row_posterior.h) at tiles of 512 and 256 samples: the
+    sizes at which one of them ends a tile exactly, one short or one over; 32x32 is the LDS cap of both."""
     c = standalone_case(S, seed=1)
-    ez, en = GRIDS["7x5"]
+    ez, en = GRIDS[grid]
     nhi = 10.0 ** c["log_nhi"]
     planes = level_planes(c["ll"], c["offset"], c["log_nhi"], nhi, c["min_z"], c["max_z"], ez, en, base_sample_inds=c["base"])
     summ = posterior_summary(c["ll"], c["offset"], c["log_nhi"], nhi, c["min_z"], c["max_z"], base_sample_inds=c["base"],
@@ -176,6 +179,44 @@ def test_single_sample_levels_land_on_the_map_pairs():
             np.add.at(want, (iz[inside], inn[inside]), 1.0)
             assert _same(planes[r, d, 0], want), (d, r)
     assert planes[:, :, 0].sum() >= 0.9 * R * 10
+
+
+def test_void_chains_are_void_for_the_map_walk_and_the_sample_walk():
+    """The MAP walk of posterior_summary and the per-sample walk of level_planes are one function
+    (csrc/row_posterior.h walk_chain).  Hand-written base indices, one finite sample per (level, row): row 0 has
+    complete chains; row 1's level-4 chain breaks at its deepest step (-1); row 2's first base index is S at every
+    level >= 2.  The MAP pairs are NaN in exactly the (row, level, slot) where level_planes puts no mass, and
+    finite where it puts 1.0."""
+    S, D, R = 5, 4, 3
+    ll = np.full((D, R, S), np.nan)
+    for d in range(D):
+        ll[d, :, d] = -50.0 - d                       # the only sample of level d + 1 is sample d
+    base = np.empty((D - 1, R, S), dtype=np.int32)
+    base[0, :], base[1, :], base[2, :] = [2, 3, 4, 0, 1], [1, 2, 3, 4, 0], [4, 0, 1, 2, 3]
+    # row 0: 1 -> 3;  2 -> 3 -> 0;  3 -> 2 -> 3 -> 0
+    base[2, 1, 3], base[1, 1, 0], base[0, 1, 4] = 0, 4, -1          # row 1, level 4: 3 -> 0 -> 4 -> void
+    base[0, 2, 1] = base[1, 2, 2] = base[2, 2, 3] = S               # row 2: the first step leaves [0, S)
+    chains = {(0, 1): [1, 3], (0, 2): [2, 3, 0], (0, 3): [3, 2, 3, 0], (1, 1): [1, 3], (1, 2): [2, 3, 0]}
+    chains.update({(r, 0): [0] for r in range(R)})                   # every other (row, level) is void
+    offset, log_nhi = np.array([0.1, 0.3, 0.5, 0.7, 0.9]), np.array([20.2, 20.8, 21.4, 22.0, 22.6])
+    min_z, max_z = np.array([2.0, 2.1, 2.2]), np.array([3.5, 3.9, 4.1])
+    ez, en = GRIDS["32x32"]
+    planes = level_planes(ll, offset, log_nhi, 10.0 ** log_nhi, min_z, max_z, ez, en, base_sample_inds=base)
+    summ = posterior_summary(ll, offset, log_nhi, 10.0 ** log_nhi, min_z, max_z, base_sample_inds=base)
+    assert np.array_equal(summ["map_sample_inds"], np.repeat(np.arange(D)[:, None], R, axis=1))
+    for d in range(D):
+        for r in range(R):
+            z, n = summ["MAP_z_dlas"][d, r], summ["MAP_log_nhis"][d, r]
+            chain = chains.get((r, d), [])
+            finite = np.arange(D) < len(chain)
+            assert np.array_equal(~np.isnan(z), finite) and np.array_equal(~np.isnan(n), finite), (d, r)
+            assert np.array_equal(n[finite], log_nhi[chain]), (d, r)
+            want = np.zeros((ez.size - 1, en.size - 1))
+            iz, inn = SO.bin_index(ez, z[finite]), SO.bin_index(en, n[finite])
+            assert (iz >= 0).all() and (inn >= 0).all()                  # every absorber is inside the grid
+            np.add.at(want, (iz, inn), 1.0)
+            assert _same(planes[r, d, 0], want), (d, r)                  # mass 1.0 per pair; none where void
+            assert planes[r, d, 0].sum() == len(chain)
 
 
 # ------------------------------------------------------------------- 5. the engine
