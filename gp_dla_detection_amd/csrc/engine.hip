@@ -429,6 +429,12 @@ int gpdla_engine_create(int32_t device, const gpdla_model* model, const gpdla_sa
     if (!(samples->nhi_samples[i] >= 0.0 && samples->nhi_samples[i] < INFINITY))
       return set_error(GPDLA_EINVAL, "nhi_samples[%lld] = %g: column densities must be finite and >= 0",
                        (long long)i, samples->nhi_samples[i]);
+  // offsets: any finite value (z_DLA = zmin + (zmax - zmin) offset, process_qsos.m:163-165, outside
+  // [0, 1] included); a NaN would make the sort below compare without a strict weak order
+  for (int64_t i = 0; i < samples->num_samples; ++i)
+    if (!std::isfinite(samples->offset_samples[i]))
+      return set_error(GPDLA_EINVAL, "offset_samples[%lld] = %g: offsets must be finite",
+                       (long long)i, samples->offset_samples[i]);
 
   HIP_TRY(hipSetDevice(device));
   gpdla_engine* e = new gpdla_engine();

@@ -96,7 +96,7 @@ typedef struct gpdla_model {
 /* DLA parameter samples (dla_samples.mat, read at process_qsos.m:38-40).  Host memory. */
 typedef struct gpdla_samples {
   int64_t num_samples;           /* S (set_parameters.m:48) */
-  const double* offset_samples;  /* [S] in [0,1] */
+  const double* offset_samples;  /* [S] in [0,1]; any finite value is accepted, NaN / inf is GPDLA_EINVAL */
   const double* nhi_samples;     /* [S] N_HI in cm^-2 (10.^log_nhi_samples) */
 } gpdla_samples;
 
