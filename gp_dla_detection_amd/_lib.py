@@ -152,6 +152,19 @@ class LevelPopulation(C.Structure):
                 ("large_inds", i32p), ("large_probs", dp), ("large_bins", i32p)]
 
 
+class BootstrapSpec(C.Structure):
+    _fields_ = [("seed", C.c_uint64 * 2), ("num_replicas", C.c_int64), ("first_replica", C.c_int64),
+                ("num_strata", C.c_int32), ("stratum_offsets", i64p), ("members", i32p)]
+
+
+def bootstrap_tiling() -> dict:
+    """The compile-time shape of the bootstrap sums kernel (gpdla_bootstrap_tiling): replicas and columns per
+    block tile, spectra per K stage, spectra per split-K slice, most replicas per device chunk."""
+    v = [C.c_int32() for _ in range(5)]
+    check(load().gpdla_bootstrap_tiling(*[C.byref(x) for x in v]))
+    return dict(zip(("tile_m", "tile_n", "stage_k", "k_slice", "max_chunk"), (x.value for x in v)))
+
+
 class DlaPrior(C.Structure):
     _fields_ = [("alpha", C.c_double), ("uniform_min", C.c_double), ("uniform_max", C.c_double),
                 ("fit_min", C.c_double), ("fit_max", C.c_double), ("fit_upper", C.c_double)]
@@ -208,6 +221,14 @@ SIGNATURES = {
     "gpdla_population_split_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, dp,
                                              C.POINTER(PopulationSpec), dp, i32p, dp, i32p]),
     "gpdla_poisson_binomial_pmf_f64": (C.c_int, [C.c_int32, dp, i64p, C.c_int64, dp]),
+    "gpdla_bootstrap_tiling": (C.c_int, [i32p, i32p, i32p, i32p, i32p]),
+    "gpdla_bootstrap_counts_i32": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(BootstrapSpec), i32p]),
+    "gpdla_bootstrap_rows_f64": (C.c_int, [C.c_int32, dp, C.c_int32, dp, dp, u8p, C.c_int64, C.c_int32, C.c_int32,
+                                           C.c_double, dp, C.c_int64]),
+    "gpdla_bootstrap_sums_f64": (C.c_int, [C.c_int32, i32p, dp, C.c_int64, C.c_int64, C.c_int64, dp]),
+    "gpdla_bootstrap_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.POINTER(BootstrapSpec), dp]),
+    "gpdla_spectrum_snrs_f32": (C.c_int, [C.c_int32, C.c_int64, i64p, fp, fp, fp, dp, dp, fp]),
+    "gpdla_spectrum_snrs_f64": (C.c_int, [C.c_int32, C.c_int64, i64p, dp, dp, dp, dp, dp, dp]),
     "gpdla_resample_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, i32p]),
     "gpdla_voigt_f64": (C.c_int, [dp, C.c_int64, C.c_double, C.c_double, C.c_int32, dp]),
     "gpdla_voigt_batch_f64": (C.c_int, [dp, C.c_int64, dp, dp, C.c_int64, C.c_int32, dp]),

@@ -355,6 +355,180 @@ def omega_dla(out, keep=None, p_thresh_spec: float = 0.05, hubble: float = 0.7, 
     return (ez[1:] + ez[:-1]) / 2.0, mean * conversion, np.sqrt(variance) * conversion, ez
 
 
+def bootstrap_strata(min_z_dlas, max_z_dlas, num_strata: int = 9, min_per_stratum: int = 10):
+    """The redshift strata ``resample`` draws within (calc_cddf.py:139-156), so that a replica keeps the rare
+    high-redshift sightlines: ``num_strata + 1`` linearly spaced edges between ``newmin`` and ``newmax`` --
+    ``newmax`` from max(max_z) - 0.2 down in steps of 0.2 until ``min_per_stratum`` spectra lie above it,
+    ``newmin`` from min(min_z) + 0.2 up in steps of 0.2 while fewer than ``min_per_stratum`` spectra have
+    ``max_z <= newmin`` (the reference's own loop, :145, counts ``min_z > newmin`` and cannot end once entered)
+    -- the first edge then replaced by min(min_z) and the last by max(max_z), and spectrum q in the stratum with
+    ``zm < max_z[q] <= zp``.  Spectra with a NaN range, or a ``max_z`` at or below the first edge, are in none.
+    A stratum below ``min_per_stratum`` raises ``ValueError``, as the reference asserts (:153).  Returns CSR:
+    (stratum_offsets [num_strata + 1] int64, members int32, ascending within a stratum)."""
+    zmin = np.asarray(min_z_dlas, dtype=np.float64).ravel()
+    zmax = np.asarray(max_z_dlas, dtype=np.float64).ravel()
+    if zmin.size != zmax.size:
+        raise ValueError("one search range per spectrum")
+    if num_strata < 1 or min_per_stratum < 1:
+        raise ValueError("num_strata and min_per_stratum must be positive")
+    ok = ~(np.isnan(zmin) | np.isnan(zmax))
+    if np.count_nonzero(ok) < min_per_stratum:
+        raise ValueError(f"{np.count_nonzero(ok)} spectra with a search range: fewer than min_per_stratum = {min_per_stratum}")
+    lo, hi = float(zmin[ok].min()), float(zmax[ok].max())
+    with np.errstate(invalid="ignore"):
+        newmax = hi - 0.2
+        while np.count_nonzero(zmax > newmax) < min_per_stratum:
+            newmax -= 0.2
+        newmin = lo + 0.2
+        while np.count_nonzero(zmax <= newmin) < min_per_stratum:
+            newmin += 0.2
+        edges = np.linspace(newmin, newmax, num_strata + 1)
+        edges[-1], edges[0] = hi, lo
+        groups = [np.flatnonzero((zmax > zm) & (zmax <= zp)) for zm, zp in zip(edges[:-1], edges[1:])]
+    for s, g in enumerate(groups):
+        if g.size < min_per_stratum:
+            raise ValueError(f"stratum {s} ({edges[s]:.3f} < max_z <= {edges[s + 1]:.3f}) holds {g.size} spectra: "
+                             f"fewer than min_per_stratum = {min_per_stratum}")
+    offsets = np.zeros(num_strata + 1, dtype=np.int64)
+    np.cumsum([g.size for g in groups], out=offsets[1:])
+    return offsets, np.concatenate(groups).astype(np.int32)
+
+
+def path_columns(z_edges, min_z_dlas, max_z_dlas, keep=None, omega_m: float = 0.279) -> np.ndarray:
+    """Every spectrum's own term of ``path_length``, Q x (nz + 1): one column per bin of ``z_edges`` and one for
+    its whole range, 0 where the search range misses the interval or ``keep`` is false (no p_dla cut,
+    calc_cddf.py:347) -- the same ``absorption_distance`` expressions, so a column's ``fsum`` is ``path_length``."""
+    ez = np.asarray(z_edges, dtype=np.float64).ravel()
+    zmin = np.asarray(min_z_dlas, dtype=np.float64).ravel()
+    zmax = np.asarray(max_z_dlas, dtype=np.float64).ravel()
+    kept = np.ones(zmin.size, dtype=bool) if keep is None else np.asarray(keep, dtype=bool).ravel()
+    cols = np.zeros((zmin.size, ez.size))
+    with np.errstate(invalid="ignore"):
+        for c, (z_lo, z_hi) in enumerate(list(zip(ez[:-1], ez[1:])) + [(ez[0], ez[-1])]):
+            use = (zmin < z_hi) & (zmax > z_lo) & kept
+            hi, lo = np.minimum(z_hi, zmax[use]), np.maximum(z_lo, zmin[use])
+            cols[use, c] = absorption_distance(hi, omega_m) - absorption_distance(lo, omega_m)
+    return cols
+
+
+def _first_column(v) -> np.ndarray:
+    """MATLAB's x(i) on a Q x D array: column 1."""
+    v = np.asarray(v, dtype=np.float64)
+    return v.reshape(v.shape[0], -1)[:, 0] if v.ndim > 1 else v
+
+
+def bootstrap_moments(out, replicas: int, seed, keep=None, strata="auto", levels: str = "first", device: int = 0,
+                      sums=None, p_thresh_spec: float = 0.05, omega_m: float = 0.279, first_replica: int = 0) -> dict:
+    """``resample`` (calc_cddf.py:126-156) and the sums behind ``line_density`` / ``omega_dla`` for ``replicas``
+    bootstrap replicas of the sightlines of ``out`` (``process_qsos(summaries=...)``) at once, on the device: the
+    per-spectrum terms of ``cddf_moments`` (``engine.bootstrap_rows``) with the ``path_columns`` appended, then
+    the stratified draws and the product counts x rows (``engine.bootstrap``).
+
+    ``seed`` is the 128-bit Philox key; replica r is the same whatever else the call holds.  ``strata`` is
+    ``"auto"`` (``bootstrap_strata`` of the search ranges), ``None`` (one stratum of all spectra) or a
+    (stratum_offsets, members) pair.  Only full-size replicas are drawn: a stratum draws as many sightlines as
+    it holds.  ``levels="all"`` uses ``bin_planes_levels`` with ``model_posteriors[:, 1:1 + D]``.
+
+    ``sums(planes=, p_dlas=, level_posteriors=, keep=, p_thresh_spec=, path=, replicas=, first_replica=, seed=,
+    stratum_offsets=, members=)`` replaces the device (tests; it returns the replicas x N sums, N = 4 nz nn +
+    nz + 1 in the order means, variance terms, moment means, moment variance terms, path per bin, whole path).
+
+    Returns per replica ``means``, ``variances``, ``moment_means``, ``moment_variances`` (B x nz x nn; what
+    ``cddf_moments`` returns), ``path`` (B x nz) and ``path_total`` (B)."""
+    from . import engine as E
+    all_levels = _check_levels(levels)
+    p = np.asarray(out["p_dlas"], dtype=np.float64).ravel()
+    zmin, zmax = _first_column(out["min_z_dlas"]), _first_column(out["max_z_dlas"])
+    if all_levels:
+        planes = np.asarray(out["bin_planes_levels"], dtype=np.float64)
+        if planes.ndim == 4:
+            planes = planes[:, None]
+        P = np.asarray(out["model_posteriors"], dtype=np.float64).reshape(planes.shape[0], -1)[:, 1:1 + planes.shape[1]]
+    else:
+        planes, P = np.asarray(out["bin_planes"], dtype=np.float64), None
+    Q = planes.shape[0]
+    nz, nn = planes.shape[-2:]
+    nb = nz * nn
+    if isinstance(strata, str):
+        if strata != "auto":
+            raise ValueError("strata must be 'auto', None or (stratum_offsets, members)")
+        strata = bootstrap_strata(zmin, zmax)
+    so, mem = (np.array([0, Q], dtype=np.int64), np.arange(Q, dtype=np.int32)) if strata is None else strata
+    path = path_columns(out["bin_z_edges"], zmin, zmax, keep, omega_m)
+    if sums is not None:
+        got = np.asarray(sums(planes=planes, p_dlas=p, level_posteriors=P, keep=keep, p_thresh_spec=p_thresh_spec, path=path,
+                              replicas=replicas, first_replica=first_replica, seed=seed, stratum_offsets=so, members=mem),
+                         dtype=np.float64)
+    else:
+        rows = E.bootstrap_rows(planes, p, keep, p_thresh_spec, P, columns=4 * nb + nz + 1, device=device)
+        rows[:, 4 * nb:] = path
+        got = E.bootstrap(rows, replicas, seed, so, mem, first_replica, device=device)
+    if got.shape != (replicas, 4 * nb + nz + 1):
+        raise ValueError(f"sums must be {(replicas, 4 * nb + nz + 1)}")
+    B = got.shape[0]
+    means, moments = got[:, :nb].reshape(B, nz, nn), got[:, 2 * nb:3 * nb].reshape(B, nz, nn)
+    return dict(means=means, variances=got[:, nb:2 * nb].reshape(B, nz, nn) + means, moment_means=moments,
+                moment_variances=got[:, 3 * nb:4 * nb].reshape(B, nz, nn) + moments,
+                path=got[:, 4 * nb:4 * nb + nz].copy(), path_total=got[:, 4 * nb + nz].copy())
+
+
+def sample_errors(out, replicas: int = 1000, seed=0, keep=None, strata="auto", levels: str = "first", device: int = 0,
+                  sums=None, p_thresh_spec: float = 0.05, hubble: float = 0.7, omega_m: float = 0.279) -> dict:
+    """``get_sample_errors`` (calc_cddf.py:162-184): the spread of dN/dX and Omega_DLA over bootstrap replicas
+    of the sightline sample, per z bin of the summary grid of ``out``.  dN/dX of a replica is
+    ``means.sum(-1) / path`` and Omega_DLA the moment estimator of ``omega_dla`` (``moment_means.sum(-1)`` times
+    its conversion at the replica's own path; in ``omega_dla``'s units, where the reference multiplies by 1000
+    and uses ``omega_dla_cddf``); a replica without path in a bin is NaN there and the percentiles ignore it.
+    Bins whose full-sample path is 0 are dropped, as in ``line_density``.
+
+    Returns ``z`` (bin centres), and for ``dndx`` and ``omega`` the reference's five products:
+    ``<name>_median`` (``dndx_sample`` / ``omega_sample``), ``<name>_68`` (2 x bins: the 84th and the 16th
+    percentile, the reference's order, :179) and ``<name>_95`` (97.5th and 2.5th); also the replica arrays
+    ``dndx_replicas`` / ``omega_replicas`` (B x bins).  The arguments are ``bootstrap_moments``'s."""
+    import warnings
+    bm = bootstrap_moments(out, replicas, seed, keep, strata, levels, device, sums, p_thresh_spec, omega_m)
+    ez = np.asarray(out["bin_z_edges"], dtype=np.float64).ravel()
+    zmin, zmax = _first_column(out["min_z_dlas"]), _first_column(out["max_z_dlas"])
+    full = np.array([path_length(a, b, zmin, zmax, keep, omega_m) for a, b in zip(ez[:-1], ez[1:])])
+    ii = full > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dX = np.where(bm["path"] > 0, bm["path"], np.nan)
+        dndx = bm["means"].sum(axis=-1) / dX
+        conversion = PROTON_MASS_G * (H100_PER_S * hubble) / LIGHT_CM_PER_S / dX / rho_crit()
+        omega = bm["moment_means"].sum(axis=-1) * conversion
+    res = dict(z=((ez[1:] + ez[:-1]) / 2.0)[ii])
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)      # a bin without path in every replica: all NaN
+        for name, v in (("dndx", dndx[:, ii]), ("omega", omega[:, ii])):
+            res[f"{name}_median"] = np.nanmedian(v, axis=0)
+            res[f"{name}_68"] = np.array((np.nanpercentile(v, 100 - 32 / 2, axis=0), np.nanpercentile(v, 32 / 2, axis=0)))
+            res[f"{name}_95"] = np.array((np.nanpercentile(v, 100 - 5 / 2, axis=0), np.nanpercentile(v, 5 / 2, axis=0)))
+            res[f"{name}_replicas"] = v
+    return res
+
+
+def compute_snrs(preloaded, out, device: int = 0) -> np.ndarray:
+    """``compute_all_snrs`` (calc_cddf.py:959-976): ``find_snr`` of every searched spectrum, on the device
+    (``engine.spectrum_snrs``) -- the number behind the ``keep`` masks of the functions above (e.g.
+    ``keep = snrs > 4``).  ``preloaded`` holds the cells ``all_wavelengths``, ``all_flux``,
+    ``all_noise_variance`` and, if present, ``all_normalizers``; ``out`` the ``max_z_dlas`` of the searched
+    spectra and, when the cells cover the whole catalogue, ``test_ind`` (a boolean mask or 0-based indices, as in
+    ``write_ascii_catalog``).  float32 cells give float32 SNRs, anything else float64."""
+    from .engine import spectrum_snrs
+    zmax = _first_column(out["max_z_dlas"])
+    cells = [list(preloaded[k]) for k in ("all_wavelengths", "all_flux", "all_noise_variance")]
+    norm = preloaded.get("all_normalizers") if hasattr(preloaded, "get") else None
+    norm = None if norm is None else np.asarray(norm, dtype=np.float64).ravel()
+    if "test_ind" in out and len(cells[0]) != zmax.size:
+        ti = np.asarray(out["test_ind"]).ravel()
+        sel = np.flatnonzero(ti) if ti.dtype == bool else ti.astype(np.int64)
+        cells = [[c[i] for i in sel] for c in cells]
+        norm = None if norm is None else norm[sel]
+    if len(cells[0]) != zmax.size:
+        raise ValueError("the preloaded cells and max_z_dlas disagree on the number of spectra")
+    return spectrum_snrs(*cells, zmax, norm, device=device)
+
+
 def _fmt(spec: str, value) -> str:
     """C / MATLAB fprintf of one number; MATLAB spells the non-finite values NaN, Inf, -Inf."""
     if isinstance(value, (float, np.floating)) and not np.isfinite(value):

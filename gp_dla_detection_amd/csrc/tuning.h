@@ -46,3 +46,20 @@
 #ifndef GPDLA_BST_USPARE
 #define GPDLA_BST_USPARE 0.40f
 #endif
+
+// bootstrap_gemm_kernel (bootstrap.hip): waves per block (32 replicas each; a block is 32 x waves replicas
+// by 128 columns), spectra per LDS stage, spectra per split-K slice (a multiple of the stage) and the most
+// replicas of one device chunk (a multiple of the block's replicas).  The slice fixes the reduction order
+// over the spectra; chosen for the DR12Q shape (profiles/bootstrap), not swept.
+#ifndef GPDLA_BOOT_WAVES
+#define GPDLA_BOOT_WAVES 4
+#endif
+#ifndef GPDLA_BOOT_STAGE_K
+#define GPDLA_BOOT_STAGE_K 16
+#endif
+#ifndef GPDLA_BOOT_KSLICE
+#define GPDLA_BOOT_KSLICE 16384
+#endif
+#ifndef GPDLA_BOOT_MAX_CHUNK
+#define GPDLA_BOOT_MAX_CHUNK 1024
+#endif

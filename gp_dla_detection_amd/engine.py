@@ -864,6 +864,125 @@ def population_split_levels(log_likelihoods, offset_samples, log_nhi_samples, mi
                 population_level_large_bins=bins)
 
 
+def _bootstrap_spec(Q: int, replicas: int, seed, first_replica: int, stratum_offsets, members):
+    """gpdla_bootstrap_spec and the arrays it points to.  ``seed`` is an integer below 2^128 (key words
+    seed mod 2^64, seed >> 64) or a pair of 64-bit words; ``stratum_offsets`` / ``members`` None: one stratum
+    of all Q spectra."""
+    if isinstance(seed, (int, np.integer)):
+        seed = (int(seed) & (2 ** 64 - 1), int(seed) >> 64)
+    k0, k1 = (int(s) for s in seed)
+    if not (0 <= k0 < 2 ** 64 and 0 <= k1 < 2 ** 64):
+        raise ValueError("seed must fit 128 bits")
+    if members is None:
+        stratum_offsets, members = [0, Q], np.arange(Q)
+    so = np.ascontiguousarray(stratum_offsets, dtype=np.int64).ravel()
+    mem = np.ascontiguousarray(members, dtype=np.int32).ravel()
+    if so.size < 2 or so[-1] != mem.size:
+        raise ValueError("stratum_offsets must have num_strata + 1 entries ending at len(members)")
+    spec = L.BootstrapSpec(seed=(C.c_uint64 * 2)(k0, k1), num_replicas=int(replicas), first_replica=int(first_replica),
+                           num_strata=so.size - 1, stratum_offsets=L.ptr(so, C.c_int64), members=L.ptr(mem, C.c_int32))
+    return spec, (so, mem)
+
+
+def bootstrap_counts(Q: int, replicas: int, seed, stratum_offsets=None, members=None, first_replica: int = 0,
+                     device: int = 0) -> np.ndarray:
+    """gpdla_bootstrap_counts_i32: the multiplicities of ``replicas`` stratified bootstrap replicas of Q
+    spectra, replicas x Q int32 (the draw rule is in include/gpdla.h "Bootstrap sample errors")."""
+    spec, _hold = _bootstrap_spec(Q, replicas, seed, first_replica, stratum_offsets, members)
+    counts = np.empty((max(int(replicas), 0), max(int(Q), 0)), dtype=np.int32)
+    L.check(L.load().gpdla_bootstrap_counts_i32(device, int(Q), C.byref(spec), L.ptr(counts, C.c_int32)))
+    return counts
+
+
+def bootstrap_rows(bin_planes, p_dlas, keep=None, p_thresh_spec: float = 0.05, level_posteriors=None, columns: int = 0,
+                   device: int = 0) -> np.ndarray:
+    """gpdla_bootstrap_rows_f64: per spectrum the four planes ``catalog.cddf_moments`` accumulates -- p A and
+    p B - p p C for ``moment=False``, then for ``moment=True`` -- as Q x max(columns, 4 nz nn); the columns past
+    4 nz nn are left 0 for the caller (the path terms).  ``bin_planes`` is Q x 5 x nz x nn, or with
+    ``level_posteriors`` (Q x D) Q x D x 5 x nz x nn, the row then the sum over the levels."""
+    planes = np.ascontiguousarray(bin_planes, dtype=np.float64)
+    if level_posteriors is None:
+        if planes.ndim != 4 or planes.shape[1] != L.SUMMARY_PLANES:
+            raise ValueError("bin_planes must be Q x 5 x nz x nn")
+        Q, D, P = planes.shape[0], 1, None
+    else:
+        if planes.ndim == 4:
+            planes = planes[:, None]
+        if planes.ndim != 5 or planes.shape[2] != L.SUMMARY_PLANES:
+            raise ValueError("bin_planes must be Q x D x 5 x nz x nn")
+        Q, D = planes.shape[:2]
+        P = np.ascontiguousarray(level_posteriors, dtype=np.float64).reshape(Q, -1)
+        if P.shape[1] != D:
+            raise ValueError("level_posteriors must be Q x D")
+    nz, nn = planes.shape[-2:]
+    p = np.ascontiguousarray(p_dlas, dtype=np.float64).ravel()
+    if p.size != Q:
+        raise ValueError("one p_dla per spectrum")
+    k = None if keep is None else np.ascontiguousarray(np.asarray(keep, dtype=bool).ravel(), dtype=np.uint8)
+    if k is not None and k.size != Q:
+        raise ValueError("one keep flag per spectrum")
+    ld = max(int(columns), 4 * nz * nn)
+    rows = np.zeros((Q, ld))
+    L.check(L.load().gpdla_bootstrap_rows_f64(device, L.ptr(planes), D, L.ptr(p), L.ptr(P), L.ptr(k, C.c_uint8), Q, nz, nn,
+                                              float(p_thresh_spec), L.ptr(rows), ld))
+    return rows
+
+
+def bootstrap_sums(counts, rows, device: int = 0) -> np.ndarray:
+    """gpdla_bootstrap_sums_f64: ``counts @ rows`` (replicas x Q int32 by Q x N) on the f64 matrix cores, in a
+    reduction order over the spectra that is the same for every replica of every call."""
+    c = np.ascontiguousarray(counts, dtype=np.int32)
+    r = np.ascontiguousarray(rows, dtype=np.float64)
+    if c.ndim != 2 or r.ndim != 2 or c.shape[1] != r.shape[0]:
+        raise ValueError("counts must be replicas x Q and rows Q x N")
+    sums = np.empty((c.shape[0], r.shape[1]))
+    L.check(L.load().gpdla_bootstrap_sums_f64(device, L.ptr(c, C.c_int32), L.ptr(r), c.shape[0], c.shape[1], r.shape[1],
+                                              L.ptr(sums)))
+    return sums
+
+
+def bootstrap(rows, replicas: int, seed, stratum_offsets=None, members=None, first_replica: int = 0,
+              device: int = 0) -> np.ndarray:
+    """gpdla_bootstrap_f64: the draws and the sums in one call, the counts never leaving the device; bit for
+    bit ``bootstrap_sums(bootstrap_counts(...), rows)``.  Returns replicas x N."""
+    r = np.ascontiguousarray(rows, dtype=np.float64)
+    if r.ndim != 2:
+        raise ValueError("rows must be Q x N")
+    spec, _hold = _bootstrap_spec(r.shape[0], replicas, seed, first_replica, stratum_offsets, members)
+    sums = np.empty((max(int(replicas), 0), r.shape[1]))
+    L.check(L.load().gpdla_bootstrap_f64(device, L.ptr(r), r.shape[0], r.shape[1], C.byref(spec), L.ptr(sums)))
+    return sums
+
+
+def spectrum_snrs(wavelengths, flux, noise_variance, max_z_dlas, normalizers=None, device: int = 0) -> np.ndarray:
+    """gpdla_spectrum_snrs_f32 / _f64: ``find_snr`` (calc_cddf.py:906-924) of every spectrum.  The three cell
+    lists hold one vector per spectrum, all float32 (the f32 call, float32 result) or anything else (taken as
+    float64)."""
+    cells = [list(wavelengths), list(flux), list(noise_variance)]
+    Q = len(cells[0])
+    if not (len(cells[1]) == len(cells[2]) == Q):
+        raise ValueError("one cell per spectrum in each list")
+    single = Q > 0 and all(np.asarray(c).dtype == np.float32 for lst in cells for c in lst)
+    dt, ct = (np.float32, C.c_float) if single else (np.float64, C.c_double)
+    offsets = np.zeros(Q + 1, dtype=np.int64)
+    np.cumsum([np.size(c) for c in cells[0]], out=offsets[1:])
+    flat = []
+    for lst in cells:
+        if any(np.size(c) != offsets[q + 1] - offsets[q] for q, c in enumerate(lst)):
+            raise ValueError("a spectrum's three vectors differ in length")
+        flat.append(np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=dt).ravel() for c in lst])
+                                         if Q else np.zeros(0, dtype=dt)))
+    zmax = np.ascontiguousarray(max_z_dlas, dtype=np.float64).ravel()
+    norm = None if normalizers is None else np.ascontiguousarray(normalizers, dtype=np.float64).ravel()
+    if zmax.size != Q or (norm is not None and norm.size != Q):
+        raise ValueError("one max_z_dla (and normalizer) per spectrum")
+    snrs = np.empty(Q, dtype=dt)
+    fn = L.load().gpdla_spectrum_snrs_f32 if single else L.load().gpdla_spectrum_snrs_f64
+    L.check(fn(device, Q, L.ptr(offsets, C.c_int64), L.ptr(flat[0], ct), L.ptr(flat[1], ct), L.ptr(flat[2], ct), L.ptr(zmax),
+               L.ptr(norm), L.ptr(snrs, ct)))
+    return snrs
+
+
 def poisson_binomial_pmf_csr(probs, offsets, device: int = 0) -> np.ndarray:
     """gpdla_poisson_binomial_pmf_f64: the coefficients of prod_j (1 - p_j + p_j x) of every bin of a CSR
     trial list, concatenated (bin b at ``offsets[b] + b``, ``n_b + 1`` values)."""

@@ -842,6 +842,15 @@ def save_dla_samples(path: str, samples: dict, **extra) -> None:
     savemat73(path, var)
 
 
+def save_snrs(path: str, snrs) -> None:
+    """The SNR file of ``compute_all_snrs`` (calc_cddf.py:968-970; ``catalog.compute_snrs``): one v7.3 variable
+    ``snrs``, a MATLAB 1 x Q row in the SNRs' own class (h5py sees (Q, 1), like the processed file's vectors;
+    the reference's own file holds a rank-1 dataset, which MATLAB's container has no form for)."""
+    from .matv73 import savemat73
+    v = np.asarray(snrs)
+    savemat73(path, {"snrs": (v if v.dtype == np.float32 else v.astype(np.float64)).reshape(1, -1)})
+
+
 def load_preloaded_qsos(path: str, test_ind=None) -> list[dict]:
     """process_qsos.m:45-60 (preloaded_qsos.mat cells, selected by test_ind); z_QSO is attached
     by the caller from the catalogue.  v7.3 files decode only the selected cells."""

@@ -630,6 +630,73 @@ int gpdla_preload_qsos_f32(int32_t device, int64_t num_quasars, const int64_t* o
                            float* out_wavelengths, float* out_flux, float* out_noise_variance,
                            uint8_t* out_pixel_mask, double* normalizers, float* medians);
 
+/* ---- Bootstrap sample errors -----------------------------------------------------
+ * calc_cddf.py's resample / get_sample_errors (:126-184): replicas of the sightline sample drawn with
+ * replacement, stratified by redshift, and the population sums of every replica.  A replica is a vector of
+ * multiplicities counts[Q]; its sums are the product sums[B][N] = counts[B][Q] rows[Q][N] on the f64 matrix
+ * cores, with rows the per-spectrum terms catalog.cddf_moments accumulates plus the path columns.
+ *
+ *   strata   CSR: stratum s holds the spectra members[stratum_offsets[s] .. stratum_offsets[s + 1]) (n_s >= 1
+ *            of them, every spectrum in at most one stratum); spectra in no stratum are never drawn
+ *   draws    Philox4x64-10 keyed by seed[0..1], stateless: draw g (a position in members) of replica r uses
+ *            counter (g >> 2, 0, r, 0), output word g & 3.  With u that word and s the stratum holding g, the
+ *            drawn spectrum is members[stratum_offsets[s] + mulhi64(u, n_s)] (bias n_s / 2^64).  Replica r is
+ *            first_replica + its index in the call, so a call's replicas depend on nothing else in it
+ *   sums     the reduction order over the spectra is a function of Q and the constants of
+ *            gpdla_bootstrap_tiling alone: a replica's sums do not depend on B, on first_replica, on the
+ *            chunking or on the other replicas (bit for bit); split-K partials are added in ascending order */
+typedef struct gpdla_bootstrap_spec {
+  uint64_t seed[2];                  /* the Philox key */
+  int64_t num_replicas;              /* B >= 1 */
+  int64_t first_replica;             /* >= 0 */
+  int32_t num_strata;                /* >= 1 */
+  const int64_t* stratum_offsets;    /* host [num_strata + 1], from 0, strictly increasing */
+  const int32_t* members;            /* host [stratum_offsets[num_strata]], each in 0..Q-1, none twice */
+} gpdla_bootstrap_spec;
+/* The compile-time shape of the sums kernel: replicas and columns per block tile, spectra per K stage,
+ * spectra per split-K slice, most replicas per device chunk. */
+int gpdla_bootstrap_tiling(int32_t* tile_m, int32_t* tile_n, int32_t* stage_k, int32_t* k_slice,
+                           int32_t* max_chunk);
+/* counts[B][Q] (host) of spec's replicas: a row sums to the member count, a stratum's part of it to n_s.
+ * gpdla_last_call_kernel_ms: one span per replica chunk.  GPDLA_EINVAL for B < 1, Q < 1, a member outside
+ * 0..Q-1 or listed twice, an empty stratum, first_replica < 0. */
+int gpdla_bootstrap_counts_i32(int32_t device, int64_t Q, const gpdla_bootstrap_spec* spec, int32_t* counts);
+/* The four moment planes of every spectrum (host buffers), rows[q ld_rows + 0 .. 4 nz nn): p A and
+ * p B - p p C of catalog.cddf_moments for moment = False, then the same pair for moment = True, every
+ * product and the difference rounded separately (no FMA), so they equal numpy's bit for bit.  planes is
+ * [Q][D][GPDLA_SUMMARY_PLANES][nz nn].  level_posteriors NULL (D must be 1): p = p_dlas.  Otherwise [Q][D] and a
+ * row is sum_d P_d A_d and sum_d (P_d B_d - P_d P_d C_d) from 0.0, d ascending, NaN P_d skipped.  A spectrum
+ * with p_dlas <= p_thresh_spec or NaN, or keep (NULL: all kept) 0, gets zeros.  The columns from 4 nz nn on
+ * are not written.  One span per spectrum chunk.  GPDLA_EINVAL for Q < 1, D outside 1..GPDLA_MAX_DLAS, a
+ * malformed grid, ld_rows < 4 nz nn. */
+int gpdla_bootstrap_rows_f64(int32_t device, const double* planes, int32_t D, const double* p_dlas,
+                             const double* level_posteriors, const uint8_t* keep, int64_t Q, int32_t nz, int32_t nn,
+                             double p_thresh_spec, double* rows, int64_t ld_rows);
+/* sums[B][N] = counts[B][Q] rows[Q][N] (host buffers) from the caller's counts.  Two spans per replica chunk
+ * (the product, the split-K reduction).  GPDLA_EINVAL for B, Q or N < 1, a negative count, a non-finite row
+ * entry. */
+int gpdla_bootstrap_sums_f64(int32_t device, const int32_t* counts, const double* rows, int64_t B, int64_t Q,
+                             int64_t N, double* sums);
+/* The counts made and used on the device, in replica chunks sized from free memory: bit for bit
+ * gpdla_bootstrap_counts_i32 followed by gpdla_bootstrap_sums_f64.  Three spans per chunk (draws, product,
+ * reduction).  The GPDLA_EINVAL cases of both. */
+int gpdla_bootstrap_f64(int32_t device, const double* rows, int64_t Q, int64_t N, const gpdla_bootstrap_spec* spec,
+                        double* sums);
+
+/* ---- Per-spectrum SNR (calc_cddf.py find_snr, :906-924) ------------------------------------------------
+ * Over the pixels with wavelength > 1215.67 (1 + max_z_dlas[q]) (compared in double): the flux is floored --
+ * with normalizers, flux / norm < 0.1 (in double) sets it to norm 0.1 (formed in double, rounded to the
+ * cells' class); without, flux < 0.1 sets it to 0.1 -- the ratio sqrt(noise_variance) / |flux|, numpy's
+ * median of it (the mean of the two middle values for an even count) and snr = 1 / median are formed in the
+ * cells' own class.  Any NaN ratio gives NaN, and so does an empty set.  Spectrum q's pixels are
+ * offsets[q] .. offsets[q + 1].  One span.  GPDLA_EINVAL for Q < 1 or offsets not ascending from 0. */
+int gpdla_spectrum_snrs_f32(int32_t device, int64_t Q, const int64_t* offsets, const float* wavelengths,
+                            const float* flux, const float* noise_variance, const double* max_z_dlas,
+                            const double* normalizers, float* snrs);
+int gpdla_spectrum_snrs_f64(int32_t device, int64_t Q, const int64_t* offsets, const double* wavelengths,
+                            const double* flux, const double* noise_variance, const double* max_z_dlas,
+                            const double* normalizers, double* snrs);
+
 /* Diagnostics (test support; not used by the compute path).
  * Re/Im of the Faddeeva function the line tables are fitted from (host, long double). */
 int gpdla_diag_faddeeva_w(double x, double y, double* re, double* im);
@@ -656,7 +723,8 @@ int gpdla_device_pci_bus_id(int32_t device, char* buf, int32_t len);
 /* Kernel times (ms, HIP events) of the calling thread's last call of gpdla_read_spec_f32,
  * gpdla_preload_qsos_f32, gpdla_halton_rr2_f64, gpdla_generate_dla_samples_f64 or
  * gpdla_poisson_binomial_pmf_f64, one per launch in launch order: read_spec 1; preload_qsos 3 (range
- * keys, scan, write); halton 1; generate 3 (KDE, Halton, inverse CDF); pmf 2 (chunks, all fold steps).  *count = launches recorded (0 for an empty call); at most capacity copied. */
+ * keys, scan, write); halton 1; generate 3 (KDE, Halton, inverse CDF); pmf 2 (chunks, all fold steps); the bootstrap and SNR calls as
+ * their comments say (the first 8 spans of a call are kept).  *count = launches recorded (0 for an empty call); at most capacity copied. */
 int gpdla_last_call_kernel_ms(double* ms, int32_t capacity, int32_t* count);
 
 #ifdef __cplusplus
