@@ -229,7 +229,10 @@ SIGNATURES = {
     "gpdla_bootstrap_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.POINTER(BootstrapSpec), dp]),
     "gpdla_spectrum_snrs_f32": (C.c_int, [C.c_int32, C.c_int64, i64p, fp, fp, fp, dp, dp, fp]),
     "gpdla_spectrum_snrs_f64": (C.c_int, [C.c_int32, C.c_int64, i64p, dp, dp, dp, dp, dp, dp]),
-    "gpdla_resample_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, i32p]),
+    "gpdla_count_mixture_f64": (C.c_int, [C.c_int32, dp, i32p, i64p, i64p, C.c_int64, C.c_int64, dp, C.c_int32, i32p, i32p,
+                                          dp, dp]),
+    "gpdla_count_mixture_tiling": (C.c_int, [i32p, i32p, i32p]),
+    "gpdla_resample_f64":(C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, i32p]),
     "gpdla_voigt_f64": (C.c_int, [dp, C.c_int64, C.c_double, C.c_double, C.c_int32, dp]),
     "gpdla_voigt_batch_f64": (C.c_int, [dp, C.c_int64, dp, dp, C.c_int64, C.c_int32, dp]),
     "gpdla_log_mvnpdf_low_rank_f64": (C.c_int, [dp, dp, dp, dp, C.c_int64, C.c_int32, dp]),

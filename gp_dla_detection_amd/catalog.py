@@ -2,7 +2,9 @@
 binned population moments (CDDF_analysis/calc_cddf.py ``_get_z_nhi_hist``), both from the posterior
 summaries the engine reduces on the device (``Engine.process_summaries``, ``process_qsos(summaries=...)``)
 instead of the Q x S sample array, and the population curves with their confidence bands -- f(N), dN/dX,
-Omega_DLA (calc_cddf.py) -- from the population variables (``process_qsos(population=...)``)."""
+Omega_DLA (calc_cddf.py) -- from the population variables (``process_qsos(population=...)``), Omega_DLA both as
+the moment estimator (``omega_dla``) and from the column density function with its posterior bands
+(``omega_dla_cddf``)."""
 from __future__ import annotations
 
 import os
@@ -353,6 +355,160 @@ def omega_dla(out, keep=None, p_thresh_spec: float = 0.05, hubble: float = 0.7, 
     with np.errstate(divide="ignore", invalid="ignore"):
         conversion = PROTON_MASS_G * (H100_PER_S * hubble) / LIGHT_CM_PER_S / dX / rho_crit()
     return (ez[1:] + ez[:-1]) / 2.0, mean * conversion, np.sqrt(variance) * conversion, ez
+
+
+def split_distributions_grid(out, keep=None, p_thresh_spec: float = 0.05, levels: str = "first"):
+    """``_split_distributions_single(..., nhi=True)`` (calc_cddf.py:724-778) once per redshift bin of the
+    population grid, as ``_get_omega_confidence_intervals`` asks for it (:568): for every (z bin, log N_HI bin)
+    cell the probabilities kept exactly and the mean of the Poisson approximation to the rest.  The population
+    variables, the spectrum filter, the order of a list (spectrum by spectrum, in sample order within one;
+    ``levels="all"``: level, sample, slot ascending) and the ``fsum`` of a cell's Poisson terms over the spectra
+    are ``split_distributions``'s.  Returns (lists[z][n], each an array; means, nz x nn)."""
+    import math
+    all_levels = _check_levels(levels)
+    plane, inds, probs, bins, nz, nn = _population_levels(out) if all_levels else _population(out)
+    Q = plane.shape[0]
+    p = np.asarray(out["p_dlas"], dtype=np.float64).ravel()
+    if p.size != Q:
+        raise ValueError("one p_dla per spectrum")
+    use = p > p_thresh_spec
+    if keep is not None:
+        use &= np.asarray(keep, dtype=bool).ravel()
+    lists = [[[] for _ in range(nn)] for _ in range(nz)]
+    small = [[[] for _ in range(nn)] for _ in range(nz)]
+    for q in np.flatnonzero(use):
+        if all_levels:
+            for d in range(plane.shape[1]):
+                for entry in np.flatnonzero(inds[q, d] >= 0):      # increasing sample index
+                    for fb in bins[q, d, entry]:                   # slot ascending
+                        if fb >= 0:
+                            lists[fb // nn][fb % nn].append(probs[q, d, entry])
+                for iz, ib in zip(*np.nonzero(plane[q, d] > 0)):
+                    small[iz][ib].append(plane[q, d, iz, ib])
+        else:
+            for slot in np.flatnonzero(inds[q] >= 0):              # increasing sample index
+                lists[bins[q, slot] // nn][bins[q, slot] % nn].append(probs[q, slot])
+            for iz, ib in zip(*np.nonzero(plane[q] > 0)):
+                small[iz][ib].append(plane[q, iz, ib])
+    return ([[np.array(v, dtype=np.float64) for v in row] for row in lists],
+            np.array([[math.fsum(v) for v in row] for row in small]).reshape(nz, nn))
+
+
+MIXTURE_LEVELS = (0.5, 0.5 - 0.68 / 2, 0.5 + 0.68 / 2, 0.5 - 0.95 / 2, 0.5 + 0.95 / 2)   # interval's own expressions (:996,999)
+
+
+def _column_stages(pmfs, means, atoms, tail_prob):
+    """One redshift bin's stages for ``total_column_intervals``: per log N_HI bin the Poisson-binomial pmf of
+    the exact list and the Poisson pmf of the rest, each cut to its central 1 - ``tail_prob`` as
+    ``_get_combined_levels`` cuts them (calc_cddf.py:789-796), in ascending column density.  A stage that is
+    exactly [1.0] (no exact trial, or a zero mean, :784-785) is dropped.  Returns (base, span, stages): the
+    column of every stage's first kept count, the summed column of the kept spans, and per stage
+    (probabilities, columns relative to the first kept count)."""
+    from scipy.stats import poisson
+    base, span, stages = 0.0, 0.0, []
+    for pmf, mean, atom in zip(pmfs, means, atoms):
+        pmf = np.asarray(pmf, dtype=np.float64).ravel()
+        dlow, dhigh = _interval(np.cumsum(pmf), 1 - tail_prob)
+        top = min(dhigh + 1, pmf.size)
+        kept = [(dlow, pmf[dlow:top])]
+        if mean != 0.0:
+            plow, phigh = (int(v) for v in poisson.interval(1 - tail_prob, mean))
+            kept.append((plow, poisson.pmf(np.arange(plow, phigh + 1), mean)))
+        for first, prob in kept:
+            base += first * atom
+            if prob.size == 1 and prob[0] == 1.0:
+                continue
+            span += (prob.size - 1) * atom
+            stages.append((prob, np.arange(prob.size, dtype=np.float64) * atom))
+    return base, span, stages
+
+
+def total_column_intervals(lists, means, log_nhi_edges, tail_prob: float = 1e-4, cells: int = 2 ** 20, device: int = 0,
+                           pmf=None, mixture=None):
+    """``_get_omega_confidence_intervals`` (calc_cddf.py:562-636) for every redshift bin at once: the
+    distribution of the total column T = sum_b n_b c_b, c_b = 10^(centre of log N_HI bin b) (:576), where n_b is
+    the sum of bin b's exact trials and a Poisson count, and the columns at which its cdf passes one half and
+    the 68 % and 95 % levels.  ``lists`` and ``means`` are ``split_distributions_grid``'s.
+
+    The reference multiplies lists of (value, probability) atoms out, merging atoms within 1e-3 of each other
+    and lumping 5e-4 of either tail after every bin (:599-630).  Here T lives on a lattice of ``cells`` entries:
+    every bin contributes two stages (``_column_stages``), the lattice covers the summed kept spans with step h,
+    a count k_rel above a stage's first kept one shifts by rint(k_rel c_b / h) cells (formed here in float64, so
+    the device and every oracle share the assignment), and the device convolves the stages one after the other
+    (``engine.count_mixture``).  Each stage moves an atom by at most h / 2.  The levels are
+    read off the unnormalised cdf, as the reference does.  The reference's ``tophat_prior`` branch (off by
+    default) is left out.
+
+    ``pmf(lists)`` replaces ``poisson_binomial_pmf`` and ``mixture(probs, shifts, tap_offsets, stage_offsets,
+    cells, levels)`` -> (lower, upper, mass) the device convolution (tests).  Returns (median [nz], 68 % pair
+    [nz x 2], 95 % pair [nz x 2], lattice step [nz]) in N_HI units; a bin without any stage has step 0."""
+    en = np.asarray(log_nhi_edges, dtype=np.float64).ravel()
+    means = np.asarray(means, dtype=np.float64)
+    nn = en.size - 1
+    if nn < 1 or means.ndim != 2 or means.shape[1] != nn or len(lists) != means.shape[0] or any(len(r) != nn for r in lists):
+        raise ValueError("lists must be nz x nn arrays and means nz x nn, for the nn + 1 log_nhi_edges")
+    if not (np.all(np.isfinite(en)) and np.all(np.diff(en) > 0)):
+        raise ValueError("log_nhi_edges must be finite and strictly increasing")
+    if not 0.0 < tail_prob < 0.05:
+        raise ValueError("tail_prob must lie in (0, 0.05): the 95 % levels are read off what is kept")
+    if not (np.all(np.isfinite(means)) and np.all(means >= 0)):
+        raise ValueError("means must be finite and >= 0")
+    if int(cells) != cells or cells < 1:
+        raise ValueError("cells must be a positive integer")
+    cells, nz = int(cells), means.shape[0]
+    atoms = 10.0 ** ((en[1:] + en[:-1]) / 2.0)
+    flat = [np.asarray(v, dtype=np.float64).ravel() for row in lists for v in row]
+    pmfs = poisson_binomial_pmf(flat, device=device) if pmf is None else pmf(flat)
+    bases, steps = np.zeros(nz), np.zeros(nz)
+    probs, shifts, tap_offsets, stage_offsets = [], [], [0], [0]
+    for iz in range(nz):
+        bases[iz], span, stages = _column_stages(pmfs[iz * nn:(iz + 1) * nn], means[iz], atoms, tail_prob)
+        # every stage's largest shift rounds up by at most a half, so this step keeps their sum below cells
+        room = cells - 1 - len(stages)
+        if stages and room < 1:
+            raise ValueError(f"cells = {cells} leaves no lattice for the {len(stages)} stages of redshift bin {iz}")
+        if stages:
+            steps[iz] = span / room
+        for prob, columns in stages:
+            probs.append(prob)
+            shifts.append(np.rint(columns / steps[iz]).astype(np.int64) if span > 0 else np.zeros(prob.size, dtype=np.int64))
+            tap_offsets.append(tap_offsets[-1] + prob.size)
+        stage_offsets.append(stage_offsets[-1] + len(stages))
+    probs = np.concatenate(probs) if probs else np.zeros(0)
+    shifts = np.concatenate(shifts) if shifts else np.zeros(0, dtype=np.int64)
+    args = (probs, shifts, np.array(tap_offsets, dtype=np.int64), np.array(stage_offsets, dtype=np.int64), cells,
+            np.array(MIXTURE_LEVELS))
+    if mixture is None:
+        from .engine import count_mixture
+        lower, upper, _ = count_mixture(*args, device=device)
+    else:
+        lower, upper, _ = mixture(*args)
+    lower, upper = (np.asarray(v, dtype=np.float64).reshape(nz, len(MIXTURE_LEVELS)) for v in (lower, upper))
+    value = lambda cell: bases + cell * steps     # noqa: E731
+    return (value(lower[:, 0]), np.stack([value(lower[:, 1]), value(upper[:, 2])], axis=1),
+            np.stack([value(lower[:, 3]), value(upper[:, 4])], axis=1), steps)
+
+
+def omega_dla_cddf(out, keep=None, p_thresh_spec: float = 0.05, hubble: float = 0.7, omega_m: float = 0.279,
+                   levels: str = "first", tail_prob: float = 1e-4, cells: int = 2 ** 20, device: int = 0, pmf=None,
+                   mixture=None):
+    """Omega_DLA per redshift bin from the column density function, with its 68 % and 95 % Bayesian bands
+    (calc_cddf.py:521-560, the curve ``plot_omega_dla`` draws): ``split_distributions_grid`` on the population
+    grid of ``out``, ``total_column_intervals`` for the bins with path, and the conversion m_p H_0 / (c rho_crit)
+    over the path -- here rho_crit does take ``hubble`` (:542), unlike ``omega_dla``.  ``keep`` is the SNR / z_QSO
+    mask, ``levels="all"`` counts every absorber of every multi-DLA level; ``tail_prob``, ``cells``, ``pmf`` and
+    ``mixture`` as in ``total_column_intervals``.  Bins without path are dropped (:546).  Returns (bin centres,
+    Omega_DLA, 68 % band [n x 2], 95 % band [n x 2], (lower, upper) bin half-widths)."""
+    ez = np.asarray(out["population_z_edges"], dtype=np.float64).ravel()
+    en = np.asarray(out["population_log_nhi_edges"], dtype=np.float64).ravel()
+    lists, means = split_distributions_grid(out, keep, p_thresh_spec, levels)
+    dX = np.array([path_length(a, b, out["min_z_dlas"], out["max_z_dlas"], keep, omega_m) for a, b in zip(ez[:-1], ez[1:])])
+    ii = np.flatnonzero(dX > 0)
+    mid, l68, l95, _ = total_column_intervals([lists[i] for i in ii], means[ii], en, tail_prob, cells, device, pmf, mixture)
+    conversion = PROTON_MASS_G / LIGHT_CM_PER_S * (H100_PER_S * hubble) / rho_crit(hubble)
+    cent = (ez[1:] + ez[:-1]) / 2.0
+    xerrs = (cent[ii] - ez[:-1][ii], ez[1:][ii] - cent[ii])
+    return cent[ii], conversion * mid / dX[ii], conversion * l68 / dX[ii, None], conversion * l95 / dX[ii, None], xerrs
 
 
 def bootstrap_strata(min_z_dlas, max_z_dlas, num_strata: int = 9, min_per_stratum: int = 10):

@@ -63,3 +63,16 @@
 #ifndef GPDLA_BOOT_MAX_CHUNK
 #define GPDLA_BOOT_MAX_CHUNK 1024
 #endif
+
+// mix_stage_kernel (count_mixture.hip): lattice cells per 256-thread workgroup (a multiple of 256; each thread
+// carries tile / 256 independent FMA chains, and one LDS read of a tap serves that many cells) and taps staged
+// in LDS per pass (12 bytes each).  The tile is also the step of mix_scan_kernel, so it fixes the cdf's summation
+// order.  Neither was swept; both are first guesses, timed at one shape (profiles/omega_cddf): at these
+// values the stage kernel compiles to 27 VGPRs, no scratch and 3 KiB of LDS, so neither registers nor LDS limit
+// its occupancy (8 waves per SIMD).
+#ifndef GPDLA_MIX_TILE
+#define GPDLA_MIX_TILE 1024
+#endif
+#ifndef GPDLA_MIX_TAPS
+#define GPDLA_MIX_TAPS 256
+#endif

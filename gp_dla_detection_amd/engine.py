@@ -995,6 +995,41 @@ def poisson_binomial_pmf_csr(probs, offsets, device: int = 0) -> np.ndarray:
     return out
 
 
+def count_mixture_tiling() -> dict:
+    """GPDLA_MIX_TILE, GPDLA_MIX_TAPS and GPDLA_MIX_MAX_LEVELS of the loaded library (``tile``, ``taps``,
+    ``max_levels``)."""
+    v = [C.c_int32() for _ in range(3)]
+    L.check(L.load().gpdla_count_mixture_tiling(*(C.byref(x) for x in v)))
+    return dict(zip(("tile", "taps", "max_levels"), (x.value for x in v)))
+
+
+def count_mixture(probs, shifts, tap_offsets, stage_offsets, cells: int, levels, device: int = 0, return_pmf: bool = False):
+    """gpdla_count_mixture_f64: per problem (CSR ``stage_offsets`` over stages, ``tap_offsets`` over taps) the
+    chain of sparse convolutions next[g] = sum_i probs_i cur[g - shifts_i] on a lattice of ``cells`` entries
+    from delta at cell 0, then per level the first cell with cdf >= level (``lower``) and the first occupied
+    cell strictly above the first with cdf > level (``upper``).  Returns (lower [P x L] int32, upper, mass [P])
+    and, with ``return_pmf``, the final lattices [P x cells]."""
+    p = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+    raw = np.asarray(shifts).ravel()
+    if raw.size and (raw.min() < -2 ** 31 or raw.max() >= 2 ** 31):
+        raise ValueError("shifts must fit 32 bits")
+    sh = np.ascontiguousarray(raw, dtype=np.int32)
+    to = np.ascontiguousarray(tap_offsets, dtype=np.int64).ravel()
+    so = np.ascontiguousarray(stage_offsets, dtype=np.int64).ravel()
+    lam = np.ascontiguousarray(levels, dtype=np.float64).ravel()
+    if so.size < 1 or to.size != so[-1] + 1 or to[-1] != p.size or sh.size != p.size:
+        raise ValueError("stage_offsets must have problems + 1 entries ending at the number of stages, tap_offsets "
+                         "stages + 1 entries ending at len(probs) == len(shifts)")
+    P = so.size - 1
+    lower, upper = np.zeros((P, lam.size), dtype=np.int32), np.zeros((P, lam.size), dtype=np.int32)
+    mass = np.zeros(P)
+    pmf = np.empty((P, int(cells))) if return_pmf and cells >= 1 else None
+    L.check(L.load().gpdla_count_mixture_f64(device, L.ptr(p), L.ptr(sh, C.c_int32), L.ptr(to, C.c_int64), L.ptr(so, C.c_int64),
+                                             P, int(cells), L.ptr(lam), lam.size, L.ptr(lower, C.c_int32),
+                                             L.ptr(upper, C.c_int32), L.ptr(mass), L.ptr(pmf)))
+    return (lower, upper, mass, pmf) if return_pmf else (lower, upper, mass)
+
+
 def forest_optical_depth(wavelengths, z_qso, tau_0, beta, num_forest_lines=31, device: int = 0) -> np.ndarray:
     """sum_i tau_0 c_i (1 + z_i)^beta [z_i <= z_qso] over the first ``num_forest_lines`` Lyman-series lines at
     the observed ``wavelengths`` (gpdla_forest_f64: the device function the engine's forest kernel calls)."""

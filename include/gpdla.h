@@ -697,6 +697,36 @@ int gpdla_spectrum_snrs_f64(int32_t device, int64_t Q, const int64_t* offsets, c
                             const double* flux, const double* noise_variance, const double* max_z_dlas,
                             const double* normalizers, double* snrs);
 
+/* ---- Count mixture: the total column of a redshift bin on a lattice -------------------
+ * calc_cddf.py's _get_omega_confidence_intervals (:562-636) combines the count distributions of a redshift
+ * bin's column-density bins into the distribution of T = sum_b n_b N_b.  Here T lives on a dense fp64 lattice of
+ * `cells` entries that starts as delta at cell 0, and a problem (one redshift bin) is a chain of stages, each a
+ * sparse pmf of taps (shift_i, p_i):
+ *   stage    next[g] = sum_i p_i cur[g - shift_i], one FMA chain per cell in ascending i, terms with g < shift_i
+ *            absent.  Two taps of a stage may share a shift.  A cell's value depends on its problem's taps alone:
+ *            not on the other problems of the call, on GPDLA_MIX_TILE or on GPDLA_MIX_TAPS
+ *   cdf      the inclusive prefix sum of the final lattice, in an order that cells and GPDLA_MIX_TILE fix; it
+ *            never decreases
+ *   levels   per level l in (0, 1): lower_cells = the first cell with cdf >= l; upper_cells = the first occupied
+ *            (pmf > 0) cell strictly above the first cell with cdf > l (the reference's "one past" upper end,
+ *            :986-1019); either is the last occupied cell where no such cell exists (:634-635), and 0 for a
+ *            lattice without mass.  mass = the cdf's last value (the levels are not rescaled by it)
+ * Inputs are host arrays in CSR form: problem p holds the stages stage_offsets[p] .. stage_offsets[p + 1] (none:
+ * the delta itself), stage s the taps tap_offsets[s] .. tap_offsets[s + 1].  Outputs: lower_cells / upper_cells
+ * [num_problems][num_levels], mass [num_problems] and, unless NULL, pmf [num_problems][cells], the final
+ * lattices.  GPDLA_EINVAL for a negative shift or one below its predecessor in the stage, a negative or
+ * non-finite probability, an empty stage, cells outside 1..GPDLA_MIX_MAX_CELLS, a problem whose summed largest
+ * shifts reach `cells`, a level outside (0, 1), more than GPDLA_MIX_MAX_LEVELS levels or 65535 problems.
+ * Workspace: 16 bytes per problem and cell.  gpdla_last_call_kernel_ms then reports 3 spans: the stage launches
+ * (one per stage index, over the cells that can be non-zero by then), the scan, the search. */
+#define GPDLA_MIX_MAX_LEVELS 8
+#define GPDLA_MIX_MAX_CELLS (1 << 28)
+int gpdla_count_mixture_f64(int32_t device, const double* probs, const int32_t* shifts, const int64_t* tap_offsets,
+                            const int64_t* stage_offsets, int64_t num_problems, int64_t cells, const double* levels,
+                            int32_t num_levels, int32_t* lower_cells, int32_t* upper_cells, double* mass, double* pmf);
+/* GPDLA_MIX_TILE, GPDLA_MIX_TAPS (csrc/tuning.h) and GPDLA_MIX_MAX_LEVELS of this build. */
+int gpdla_count_mixture_tiling(int32_t* tile, int32_t* taps, int32_t* max_levels);
+
 /* Diagnostics (test support; not used by the compute path).
  * Re/Im of the Faddeeva function the line tables are fitted from (host, long double). */
 int gpdla_diag_faddeeva_w(double x, double y, double* re, double* im);
@@ -721,9 +751,10 @@ int32_t gpdla_device_count(void);
  * (the multi-GPU bench reports it per rank; process_qsos.m:88's spectra loop split over devices). */
 int gpdla_device_pci_bus_id(int32_t device, char* buf, int32_t len);
 /* Kernel times (ms, HIP events) of the calling thread's last call of gpdla_read_spec_f32,
- * gpdla_preload_qsos_f32, gpdla_halton_rr2_f64, gpdla_generate_dla_samples_f64 or
- * gpdla_poisson_binomial_pmf_f64, one per launch in launch order: read_spec 1; preload_qsos 3 (range
- * keys, scan, write); halton 1; generate 3 (KDE, Halton, inverse CDF); pmf 2 (chunks, all fold steps); the bootstrap and SNR calls as
+ * gpdla_preload_qsos_f32, gpdla_halton_rr2_f64, gpdla_generate_dla_samples_f64,
+ * gpdla_poisson_binomial_pmf_f64 or gpdla_count_mixture_f64, one per launch in launch order: read_spec 1;
+ * preload_qsos 3 (range keys, scan, write); halton 1; generate 3 (KDE, Halton, inverse CDF); pmf 2 (chunks, all
+ * fold steps); count_mixture 3 (all stage launches, scan, search); the bootstrap and SNR calls as
  * their comments say (the first 8 spans of a call are kept).  *count = launches recorded (0 for an empty call); at most capacity copied. */
 int gpdla_last_call_kernel_ms(double* ms, int32_t capacity, int32_t* count);
 
