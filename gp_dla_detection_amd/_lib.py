@@ -109,6 +109,21 @@ class Summaries(C.Structure):
                 ("map_z_dlas", dp), ("map_log_nhis", dp), ("bin_planes", dp)]
 
 
+INTERVAL_MAX_LEVELS = 8
+INTERVAL_MAX_SAMPLES = 1 << 20
+
+
+class IntervalSpec(C.Structure):
+    _fields_ = [("log_nhi_samples", dp), ("lr_delta", C.c_double), ("num_levels", C.c_int32),
+                ("levels", C.c_double * INTERVAL_MAX_LEVELS)]
+
+
+class Intervals(C.Structure):
+    _fields_ = [("memory", C.c_int32), ("z_means", dp), ("z_sds", dp), ("log_nhi_means", dp), ("log_nhi_sds", dp),
+                ("z_lr_ranges", dp), ("log_nhi_lr_ranges", dp), ("z_quantiles", dp), ("log_nhi_quantiles", dp),
+                ("lr_counts", i32p)]
+
+
 class Forest(C.Structure):
     _fields_ = [("num_forest_lines", C.c_int32), ("variance_series", C.c_int32), ("mean_flux", C.c_int32),
                 ("mean_flux_tau_0", C.c_double), ("mean_flux_beta", C.c_double)]
@@ -198,6 +213,12 @@ SIGNATURES = {
     "gpdla_engine_get_summary_stats": (C.c_int, [C.c_void_p, dp, i64p]),
     "gpdla_posterior_summary_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, dp, i32p,
                                               C.c_int32, C.POINTER(SummarySpec), i32p, dp, dp, dp, dp]),
+    "gpdla_engine_process_intervals": (C.c_int, [C.c_void_p, C.POINTER(Spectra), C.POINTER(MultiDla),
+                                                 C.POINTER(ResultsMulti), C.POINTER(SummarySpec),
+                                                 C.POINTER(Summaries), C.POINTER(IntervalSpec), C.POINTER(Intervals)]),
+    "gpdla_engine_get_interval_stats": (C.c_int, [C.c_void_p, dp, i64p]),
+    "gpdla_posterior_intervals_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, i32p,
+                                                C.c_int32, C.POINTER(IntervalSpec), C.POINTER(Intervals)]),
     "gpdla_engine_set_forest": (C.c_int, [C.c_void_p, C.POINTER(Forest)]),
     "gpdla_engine_set_forest_scoped": (C.c_int, [C.c_void_p, C.POINTER(Forest), C.c_int32]),
     "gpdla_forest_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, dp]),

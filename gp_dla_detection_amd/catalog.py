@@ -755,3 +755,90 @@ def write_ascii_catalog(directory: str, test_set_name: str, catalog: dict, sampl
                               _exp3(post[i, 0]), _exp3(post[i, 1])]) + " ")
             f.write(_fmt("%06.4f", map_z[i]) + " " + _fmt("%07.4f", map_n[i]) + "\n")
     return paths
+
+
+# ------------------------------------------------------------------------------- posterior intervals
+def _interval_array(out, key, tail_dims: int) -> np.ndarray:
+    """An INTERVAL_VARIABLES array of ``process_qsos(intervals=...)``, or of its file as ``matv73.loadmat`` reads it
+    back: Q x D x 4 and ``tail_dims`` further axes."""
+    if key not in out:
+        raise ValueError(f"the run has no {key}: process_qsos(intervals=...) writes it")
+    v = np.asarray(out[key], dtype=np.float64)
+    if v.ndim != 3 + tail_dims or v.shape[2] != 4:
+        raise ValueError(f"{key} must be Q x D x 4" + " x n" * tail_dims)
+    return v
+
+
+def find_delta_nhi(out) -> np.ndarray:
+    """DLACatalogue.find_delta_NHI (calc_cddf.py:872-878) per searched spectrum: the range of log N_HI over the
+    samples of the first DLA model whose likelihood is within e^-lr_delta of the maximum -- hi - lo of level 1,
+    slot 0 of ``log_nhi_lr_ranges`` (NaN for a spectrum without such a sample)."""
+    r = _interval_array(out, "log_nhi_lr_ranges", 1)
+    return r[:, 0, 0, 1] - r[:, 0, 0, 0]
+
+
+def find_delta_z(out) -> np.ndarray:
+    """DLACatalogue.find_delta_z (calc_cddf.py:880-886): the same for z_DLA, from ``z_dla_lr_ranges``."""
+    r = _interval_array(out, "z_dla_lr_ranges", 1)
+    return r[:, 0, 0, 1] - r[:, 0, 0, 0]
+
+
+ABSORBER_FIELDS = ("spectrum", "level", "absorber", "map_z_dla", "map_log_nhi", "z_dla_mean", "z_dla_sd",
+                   "log_nhi_mean", "log_nhi_sd", "z_dla_lr_lo", "z_dla_lr_hi", "log_nhi_lr_lo", "log_nhi_lr_hi")
+
+
+def absorber_table(out) -> dict:
+    """One record per (spectrum, absorber) of each spectrum's best DLA level -- the level d with the highest
+    model posterior, as ``MAP_z_dlas`` takes it, giving d records -- as a dict of equal-length columns:
+
+    ``spectrum`` (0-based row of the run), ``level`` (d, 1-based), ``absorber`` (slot, 0 = the sample's own),
+    ``map_z_dla`` / ``map_log_nhi`` (the MAP pair), ``z_dla_quantiles`` / ``log_nhi_quantiles`` (records x L, at
+    ``interval_levels``, also returned), ``z_dla_mean`` / ``_sd``, ``log_nhi_mean`` / ``_sd`` and the
+    likelihood-ratio ranges ``z_dla_lr_lo`` / ``_hi``, ``log_nhi_lr_lo`` / ``_hi``.  ``out`` holds the variables
+    of ``process_qsos(..., intervals=...)``."""
+    zq, nq = _interval_array(out, "z_dla_quantiles", 1), _interval_array(out, "log_nhi_quantiles", 1)
+    Q, D = zq.shape[:2]
+    post = np.asarray(out["model_posteriors"], dtype=np.float64).reshape(Q, -1)[:, 1:1 + D]
+    level = np.argmax(np.where(np.isnan(post), -np.inf, post), axis=1) if Q else np.zeros(0, dtype=np.int64)
+    map_z = np.asarray(out["MAP_z_dlas"], dtype=np.float64).reshape(Q, -1)
+    map_n = np.asarray(out["MAP_log_nhis"], dtype=np.float64).reshape(Q, -1)
+    q = np.repeat(np.arange(Q), level + 1)
+    u = np.concatenate([np.arange(d + 1) for d in level]) if Q else np.zeros(0, dtype=np.int64)
+    d = level[q]
+    pick = lambda key, tail: _interval_array(out, key, tail)[q, d, u]   # noqa: E731
+    zr, nr = pick("z_dla_lr_ranges", 1), pick("log_nhi_lr_ranges", 1)
+    return dict(spectrum=q, level=d + 1, absorber=u, map_z_dla=map_z[q, u], map_log_nhi=map_n[q, u],
+                z_dla_quantiles=zq[q, d, u], log_nhi_quantiles=nq[q, d, u],
+                z_dla_mean=pick("z_dla_means", 0), z_dla_sd=pick("z_dla_sds", 0),
+                log_nhi_mean=pick("log_nhi_means", 0), log_nhi_sd=pick("log_nhi_sds", 0),
+                z_dla_lr_lo=zr[:, 0], z_dla_lr_hi=zr[:, 1], log_nhi_lr_lo=nr[:, 0], log_nhi_lr_hi=nr[:, 1],
+                interval_levels=np.asarray(out["interval_levels"], dtype=np.float64).ravel())
+
+
+def write_absorber_catalog(directory: str, test_set_name: str, catalog: dict, out: dict) -> str:
+    """``<test_set_name>_absorbers.dat`` in ``directory``: ``absorber_table(out)`` with one line per record --
+    the 9-digit thing_id (``catalog['thing_ids']`` at ``out['test_ind']``, as ``write_ascii_catalog`` resolves
+    it), level and absorber slot (1-based), the MAP pair, then for z_DLA and log N_HI in turn the quantiles in
+    level order, mean, sd and the likelihood-ratio range; a header line names the columns.  z in %06.4f and
+    log N_HI in %07.4f like the results file, the sds in %.4e.  Returns the path."""
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, f"{test_set_name}_absorbers.dat")
+    t = absorber_table(out)
+    thing_ids = np.asarray(catalog["thing_ids"], dtype=np.int64).ravel()
+    ti = np.asarray(out["test_ind"]).ravel()
+    searched = np.flatnonzero(ti) if ti.dtype == bool else ti.astype(np.int64)
+    levels = t["interval_levels"]
+    names = ["thing_id", "level", "absorber", "map_z_dla", "map_log_nhi"]
+    for prefix in ("z_dla", "log_nhi"):
+        names += [f"{prefix}_q{lv:g}" for lv in levels] + [f"{prefix}_mean", f"{prefix}_sd", f"{prefix}_lr_lo", f"{prefix}_lr_hi"]
+    with open(path, "w") as f:
+        f.write("# " + " ".join(names) + "\n")
+        for i in range(t["spectrum"].size):
+            f.write("%09d %d %d " % (thing_ids[searched[t["spectrum"][i]]], t["level"][i], t["absorber"][i] + 1))
+            fields = [_fmt("%06.4f", t["map_z_dla"][i]), _fmt("%07.4f", t["map_log_nhi"][i])]
+            for prefix, spec in (("z_dla", "%06.4f"), ("log_nhi", "%07.4f")):
+                fields += [_fmt(spec, v) for v in t[prefix + "_quantiles"][i]]
+                fields += [_fmt(spec, t[prefix + "_mean"][i]), _fmt("%.4e", t[prefix + "_sd"][i]),
+                           _fmt(spec, t[prefix + "_lr_lo"][i]), _fmt(spec, t[prefix + "_lr_hi"][i])]
+            f.write(" ".join(fields) + "\n")
+    return path

@@ -100,7 +100,8 @@ struct TimedLaunch {
              // gpdla_engine_process_multi only: 4 resample, 5 level >= 2 sweep, 6 its log-mean-exp;
              // 7 posterior summaries (gpdla_engine_process_summaries); 8 forest kernels; gpdla_engine_process_models
              // only: 9 sub-DLA sweep, 10 its log-mean-exp and MAP launches; 11 population launches
-             // (gpdla_engine_process_population); 12 level-population launches (gpdla_engine_process_levels)
+             // (gpdla_engine_process_population); 12 level-population launches (gpdla_engine_process_levels);
+             // 13 posterior intervals (gpdla_engine_process_intervals)
   int level; // multi-DLA level the span also counts for in gpdla_multi_stats (0: none)
 };
 
@@ -244,6 +245,16 @@ struct gpdla_engine {
   double level_population_ms = 0.0;
   int64_t level_population_launches = 0;
 
+  // posterior intervals (gpdla_engine_process_intervals): the offsets in the caller's order, the call's log10
+  // N_HI, the rank tables of both ([S] ranks, [S] values by rank), and a batch's outputs (one block:
+  // [4][D][nq][kMaxDlas] moments, [2][D][nq][kMaxDlas][2] ranges, [2][D][nq][kMaxDlas][levels] quantiles; [D][nq] counts)
+  std::vector<double> h_off_c;
+  double *d_i_lognhi = nullptr, *d_i_uniq = nullptr, *d_i_out = nullptr;
+  int32_t *d_i_rank = nullptr, *d_i_count = nullptr;
+  size_t cap_i_lognhi = 0, cap_i_uniq = 0, cap_i_out = 0, cap_i_rank = 0, cap_i_count = 0;
+  double interval_ms = 0.0;
+  int64_t interval_launches = 0;
+
   std::vector<TimedLaunch> pending;
   gpdla_stats stats{};
 };
@@ -275,6 +286,7 @@ int resolve_events(gpdla_engine* e) {
     if (t.kind == 10) { e->model_stats.sub_dla_reduce_ms += ms; e->model_stats.sub_dla_reduce_launches++; }
     if (t.kind == 11) { e->population_ms += ms; e->population_launches++; }
     if (t.kind == 12) { e->level_population_ms += ms; e->level_population_launches++; }
+    if (t.kind == 13) { e->interval_ms += ms; e->interval_launches++; }
     if (t.level >= 1 && t.level <= GPDLA_MAX_DLAS) {
       e->mstats.level_ms[t.level - 1] += ms;
       e->mstats.level_launches[t.level - 1]++;
@@ -382,7 +394,8 @@ void gpdla_engine_destroy(gpdla_engine* e) {
                   e->d_sub_lognhi, e->d_sub_sll, e->d_sub_ev, e->d_sub_null, e->d_sub_mll, e->d_sub_mz,
                   e->d_sub_mn, e->d_sub_mind, e->d_p_lpno, e->d_p_lpdla, e->d_p_lplls, e->d_p_lognhi, e->d_p_edges,
                   e->d_p_pdla, e->d_p_plane, e->d_p_lprob, e->d_p_lind, e->d_p_lbin,
-                  e->d_lv_post, e->d_lv_planes, e->d_lv_plane, e->d_lv_lprob, e->d_lv_lind, e->d_lv_lbin};
+                  e->d_lv_post, e->d_lv_planes, e->d_lv_plane, e->d_lv_lprob, e->d_lv_lind, e->d_lv_lbin,
+                  e->d_i_lognhi, e->d_i_uniq, e->d_i_out, e->d_i_rank, e->d_i_count};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (e->h_meta) (void)hipHostFree(e->h_meta);
@@ -1099,6 +1112,8 @@ int gpdla_engine_reset_stats(gpdla_engine* e) {
   e->population_launches = 0;
   e->level_population_ms = 0.0;
   e->level_population_launches = 0;
+  e->interval_ms = 0.0;
+  e->interval_launches = 0;
   e->model_stats = gpdla_model_stats{};
   return GPDLA_OK;
 }
@@ -1137,6 +1152,7 @@ static int multi_caller_samples(gpdla_engine* e) {
   dummy = 0;
   if ((rc = grow(&e->d_off_c, &dummy, S))) return rc;
   HIP_TRY(hipMemcpy(e->d_off_c, off_c.data(), S * 8, hipMemcpyHostToDevice));
+  e->h_off_c = off_c;
   return GPDLA_OK;
 }
 
@@ -1166,8 +1182,19 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
                               const gpdla_results_multi* res, const gpdla_summary_spec* spec,
                               const gpdla_summaries* sums, const gpdla_sub_dla* sub = nullptr,
                               const gpdla_results_sub* rsub = nullptr, const gpdla_population_spec* pspec = nullptr,
-                              const gpdla_population* pop = nullptr, const gpdla_level_population* lv = nullptr) {
+                              const gpdla_population* pop = nullptr, const gpdla_level_population* lv = nullptr,
+                              const gpdla_interval_spec* ispec = nullptr, const gpdla_intervals* iv = nullptr) {
   if (!e || !sp || !mu || !res) return set_error(GPDLA_EINVAL, "null argument");
+  if (ispec) {   // (gpdla_engine_process_intervals: iv is set)
+    if (!ispec->log_nhi_samples) return set_error(GPDLA_EINVAL, "null interval log_nhi_samples");
+    if (!iv->z_means || !iv->z_sds || !iv->log_nhi_means || !iv->log_nhi_sds || !iv->z_lr_ranges || !iv->log_nhi_lr_ranges ||
+        !iv->z_quantiles || !iv->log_nhi_quantiles || !iv->lr_counts)
+      return set_error(GPDLA_EINVAL, "null interval array");
+    if (iv->memory != GPDLA_MEM_HOST && iv->memory != GPDLA_MEM_DEVICE)
+      return set_error(GPDLA_EINVAL, "intervals memory=%d", iv->memory);
+    int rci = validate_interval_levels(ispec->lr_delta, ispec->num_levels, ispec->levels, e->S);
+    if (rci) return rci;
+  }
   // a half is asked for by its arrays: the planes by bin_planes, the posteriors and the split by the rest
   const bool lv_planes = lv && lv->bin_planes;
   const bool lv_split = lv && (lv->level_posteriors || lv->poisson_plane || lv->large_inds || lv->large_probs || lv->large_bins);
@@ -1252,7 +1279,7 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
     return set_error(GPDLA_EINVAL, "sample_ld (%lld) < num_samples (%lld)", (long long)res->sample_ld, (long long)S);
   HIP_TRY(hipSetDevice(e->device));
   int rc;
-  if ((D > 1 || spec || pspec) && (rc = multi_caller_samples(e))) return rc;
+  if ((D > 1 || spec || pspec || ispec) && (rc = multi_caller_samples(e))) return rc;
   hipStream_t st = e->stream;
   if (sub) {  // the column densities in the sweep's (ascending-offset) order, as the engine's own are kept
     const size_t Ss = (size_t)S;
@@ -1279,6 +1306,20 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
       HIP_TRY(hipMemcpyAsync(e->d_s_edges, spec->z_edges, (size_t)(nzb + 1) * 8, hipMemcpyHostToDevice, st));
       HIP_TRY(hipMemcpyAsync(e->d_s_edges + nzb + 1, spec->log_nhi_edges, (size_t)(nnb + 1) * 8, hipMemcpyHostToDevice, st));
     }
+  }
+  if (ispec) {   // the rank tables of the call's samples: [offset | log N_HI]
+    const size_t Ss = (size_t)S;
+    std::vector<int32_t> rank(2 * Ss);
+    std::vector<double> uniq(2 * Ss);
+    build_rank_table(e->h_off_c.data(), S, rank.data(), uniq.data());
+    build_rank_table(ispec->log_nhi_samples, S, rank.data() + Ss, uniq.data() + Ss);
+    if ((rc = grow(&e->d_i_lognhi, &e->cap_i_lognhi, Ss))) return rc;
+    if ((rc = grow(&e->d_i_rank, &e->cap_i_rank, 2 * Ss))) return rc;
+    if ((rc = grow(&e->d_i_uniq, &e->cap_i_uniq, 2 * Ss))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_i_lognhi, ispec->log_nhi_samples, Ss * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_i_rank, rank.data(), 2 * Ss * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_i_uniq, uniq.data(), 2 * Ss * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));   // pageable host memory: the copies have left the vectors
   }
   const int pnz = pspec ? pspec->num_z_bins : 0, pnn = pspec ? pspec->num_nhi_bins : 0;
   const size_t pbins = (size_t)pnz * pnn;
@@ -1478,6 +1519,41 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
                                (size_t)nq * kSummaryPlanes * nbins * 8, sk, st));
     }
 
+    if (ispec) {
+      const size_t Ss = (size_t)S, slots = (size_t)nq * D * kMaxDlas, nlev = (size_t)ispec->num_levels;
+      if ((rc = grow(&e->d_i_out, &e->cap_i_out, slots * (8 + 2 * nlev)))) return rc;
+      if ((rc = grow(&e->d_i_count, &e->cap_i_count, (size_t)nq * D))) return rc;
+      IntervalArgs ia{};
+      ia.r = on_grid(e->d_i_lognhi, 0, 0, nullptr);
+      ia.rank_z = e->d_i_rank; ia.rank_n = e->d_i_rank + Ss; ia.uniq_off = e->d_i_uniq; ia.uniq_n = e->d_i_uniq + Ss;
+      ia.lr_delta = ispec->lr_delta; ia.num_levels = ispec->num_levels;
+      for (size_t i = 0; i < nlev; ++i) ia.levels[i] = ispec->levels[i];
+      double* io = e->d_i_out;
+      ia.z_mean = io; ia.z_sd = io + slots; ia.n_mean = io + 2 * slots; ia.n_sd = io + 3 * slots;
+      ia.z_lr = io + 4 * slots; ia.n_lr = io + 6 * slots;
+      ia.z_q = io + 8 * slots; ia.n_q = ia.z_q + slots * nlev;
+      ia.lr_count = e->d_i_count;
+      TimedLaunch t13{};
+      if ((rc = record_start(e, &t13, 13))) return rc;
+      HIP_TRY(launch_posterior_intervals(ia, st));
+      HIP_TRY(hipEventRecord(t13.stop, st));
+      e->pending.push_back(t13);
+      const hipMemcpyKind ik = iv->memory == GPDLA_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+      const size_t per = (size_t)nq * kMaxDlas;   // slots of one level of the batch
+      for (int d = 0; d < D; ++d) {
+        const size_t src = (size_t)d * per, dst = ((size_t)d * Q + q0) * kMaxDlas;
+        HIP_TRY(hipMemcpyAsync(iv->z_means + dst, ia.z_mean + src, per * 8, ik, st));
+        HIP_TRY(hipMemcpyAsync(iv->z_sds + dst, ia.z_sd + src, per * 8, ik, st));
+        HIP_TRY(hipMemcpyAsync(iv->log_nhi_means + dst, ia.n_mean + src, per * 8, ik, st));
+        HIP_TRY(hipMemcpyAsync(iv->log_nhi_sds + dst, ia.n_sd + src, per * 8, ik, st));
+        HIP_TRY(hipMemcpyAsync(iv->z_lr_ranges + dst * 2, ia.z_lr + src * 2, per * 2 * 8, ik, st));
+        HIP_TRY(hipMemcpyAsync(iv->log_nhi_lr_ranges + dst * 2, ia.n_lr + src * 2, per * 2 * 8, ik, st));
+        HIP_TRY(hipMemcpyAsync(iv->z_quantiles + dst * nlev, ia.z_q + src * nlev, per * nlev * 8, ik, st));
+        HIP_TRY(hipMemcpyAsync(iv->log_nhi_quantiles + dst * nlev, ia.n_q + src * nlev, per * nlev * 8, ik, st));
+        HIP_TRY(hipMemcpyAsync(iv->lr_counts + (size_t)d * Q + q0, e->d_i_count + (size_t)d * nq, nq * 4, ik, st));
+      }
+    }
+
     ModelPosteriorArgs ma{};   // the posterior launches of both population halves
     if (pspec) {
       const size_t NL = kPopulationMaxLarge;
@@ -1585,6 +1661,25 @@ int gpdla_engine_process_summaries(gpdla_engine* e, const gpdla_spectra* sp, con
                                    const gpdla_summaries* sums) {
   if (!spec || !sums) return set_error(GPDLA_EINVAL, "null argument");
   return process_multi_impl(e, sp, mu, res, spec, sums);
+}
+
+int gpdla_engine_process_intervals(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
+                                   const gpdla_results_multi* res, const gpdla_summary_spec* spec,
+                                   const gpdla_summaries* sums, const gpdla_interval_spec* ispec,
+                                   const gpdla_intervals* iv) {
+  if (!spec || !sums || !ispec || !iv) return set_error(GPDLA_EINVAL, "null argument");
+  return process_multi_impl(e, sp, mu, res, spec, sums, nullptr, nullptr, nullptr, nullptr, nullptr, ispec, iv);
+}
+
+int gpdla_engine_get_interval_stats(gpdla_engine* e, double* ms, int64_t* launches) {
+  if (!e || !ms || !launches) return set_error(GPDLA_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  int rc = resolve_events(e);
+  if (rc) return rc;
+  *ms = e->interval_ms;
+  *launches = e->interval_launches;
+  return GPDLA_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -557,6 +557,31 @@ struct SummaryArgs {
 };
 hipError_t launch_posterior_summary(const SummaryArgs& a, hipStream_t s);
 
+// ---- posterior intervals (posterior_intervals.hip): per (row, level, slot) and parameter the likelihood-ratio
+// range, mean and sd, and the quantiles as weighted order statistics over the samples' dense ranks
+constexpr int kIntervalMaxLevels = 8;
+constexpr int64_t kIntervalMaxSamples = 1 << 20;
+struct IntervalArgs {
+  SampleRowsArgs r;              // no grid
+  const int32_t* rank_z;         // [S] dense rank of offset[i] among the offsets (equal values share one)
+  const int32_t* rank_n;         // [S] ... of log_nhi[i]
+  const double* uniq_off;        // [S] the offset of each rank
+  const double* uniq_n;          // [S] the log N_HI of each rank
+  double lr_delta;
+  int32_t num_levels;
+  double levels[kIntervalMaxLevels];
+  double *z_mean, *z_sd, *n_mean, *n_sd;   // [levels][rows][kMaxDlas]
+  double *z_lr, *n_lr;           // [levels][rows][kMaxDlas][2]
+  double *z_q, *n_q;             // [levels][rows][kMaxDlas][num_levels]
+  int32_t* lr_count;             // [levels][rows]
+};
+hipError_t launch_posterior_intervals(const IntervalArgs& a, hipStream_t s);
+// rank[i] = the dense rank of x[i] (ascending, equal values share a rank, NaNs last and together) and
+// uniq[r] = the value of rank r (NaN past the last rank); both [S]
+void build_rank_table(const double* x, int64_t S, int32_t* rank, double* uniq);
+// GPDLA_EINVAL with a message unless lr_delta, the quantile levels and S are usable
+int validate_interval_levels(double lr_delta, int32_t num_levels, const double* levels, int64_t S);
+
 // ---- population statistics (population.hip, level_population.hip): the model posteriors per spectrum
 // (p_dla, and the posterior P_d of each DLA level), per (row, level) the binned masses and the split of
 // P_d pi_{d,j} into a Poisson plane and a short list of large probabilities with every absorber of a sample's

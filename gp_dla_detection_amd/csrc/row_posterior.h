@@ -373,6 +373,164 @@ __device__ __forceinline__ void split_rows(const SplitArgs& a, int row, int64_t 
                                 a.large_bins + o * kPopulationMaxLarge * kBinSlots);
 }
 
+// ---- posterior intervals (posterior_intervals.hip): the mass of one absorber slot goes
+// into histograms over the dense ranks of its values, filled with scan_tile's owned-bin pattern: first coarse
+// bins rank >> s, then the 2^s ranks of the coarse bin each quantile level selected
+constexpr int kIntervalTile = 512;          // samples staged per pass: a mass and one bin per parameter
+constexpr int kIntervalCoarseBins = 1024;
+constexpr int kIntervalFineCells = 2048;    // (level, rank) cells of one parameter's fine histograms per pass
+constexpr int kIntervalQuantiles = 8;       // kIntervalMaxLevels
+// the smallest shift that leaves at most kIntervalCoarseBins bins of S ranks: 0 up to S = 1024, 10 at 2^20
+__host__ __device__ inline int interval_shift(int64_t S) {
+  int s = 0;
+  while (((S - 1) >> s) >= kIntervalCoarseBins) ++s;
+  return s;
+}
+// quantile levels whose fine histograms share a pass: all of them up to s = 8, 4 at s = 9, 2 at s = 10
+__host__ __device__ inline int interval_group(int s, int nq) {
+  const int g = kIntervalFineCells >> s;
+  return g < nq ? (g < 1 ? 1 : g) : nq;
+}
+// cells of one parameter's histogram region: the coarse bins, or the fine cells of a group if there are more
+__host__ __device__ inline int interval_cells(int64_t S, int nq) {
+  const int s = interval_shift(S);
+  const int coarse = (int)((S - 1) >> s) + 1, fine = s ? interval_group(s, nq) << s : 0;
+  return coarse > fine ? coarse : fine;
+}
+struct IntervalLds {
+  size_t red_v, red_i, res, target, base_c, base, pick_c, rank, pick, last, hist, mass, bin_z, bin_n, total;
+  __host__ __device__ size_t take(size_t bytes) { const size_t o = total; total = up16(total + bytes); return o; }
+};
+constexpr int kIntervalResults = kIntervalQuantiles + 4;   // per (parameter, slot): quantiles, mean, sd, lo, hi
+// 9,536 B + 16 B per cell: 19,536 B at S = 10^4 (625 coarse bins), 25,920 B at 1,024 bins, and at most 42,304 B
+// (2,048 fine cells: eight levels at s = 8, or any group from s = 9 on, S = 2^20 included)
+__host__ __device__ inline IntervalLds interval_lds(int64_t S, int nq) {
+  IntervalLds l{};
+  l.red_v = l.take(kRowWaves * 8);
+  l.red_i = l.take(kRowWaves * 4);
+  l.res = l.take((size_t)2 * 4 * kIntervalResults * 8);
+  l.target = l.take(2 * kIntervalQuantiles * 8);   // per parameter and level: level * T
+  l.base_c = l.take(2 * kIntervalQuantiles * 8);   // the coarse cdf before the selected bin
+  l.base = l.take(kIntervalQuantiles * 8);         // a selection's result: the cdf before the bin taken
+  l.pick_c = l.take(2 * kIntervalQuantiles * 4);   // the selected coarse bin
+  l.rank = l.take(2 * kIntervalQuantiles * 4);     // the selected rank
+  l.pick = l.take(2 * kIntervalQuantiles * 4);     // a selection: first candidate bins, then the bins taken
+  l.last = l.take(4);
+  l.hist = l.take((size_t)2 * interval_cells(S, nq) * 8);
+  l.mass = l.take((size_t)kIntervalTile * 8);
+  l.bin_z = l.take((size_t)kIntervalTile * 4);
+  l.bin_n = l.take((size_t)kIntervalTile * 4);
+  return l;
+}
+
+// sum of one value per thread in row_weight_sum's order (xor butterfly, waves in order); every thread returns
+// the same value and s_rv is free again on return
+__device__ __forceinline__ double row_sum(double loc, int tid, double* s_rv) {
+  const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) loc += __shfl_xor(loc, o);
+  if (lane == 0) s_rv[wave] = loc;
+  __syncthreads();
+  double W = s_rv[0];
+#pragma unroll
+  for (int w = 1; w < kRowWaves; ++w) W += s_rv[w];
+  __syncthreads();
+  return W;
+}
+// min (kMax false) or max over one value per thread: exact, so any order serves
+template <bool kMax>
+__device__ __forceinline__ double row_extreme(double loc, int tid, double* s_rv) {
+  const int lane = tid & 63, wave = tid >> 6;
+  auto pick = [](double a, double b) { return kMax ? (b > a ? b : a) : (b < a ? b : a); };
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) loc = pick(loc, __shfl_xor(loc, o));
+  if (lane == 0) s_rv[wave] = loc;
+  __syncthreads();
+  double v = s_rv[0];
+#pragma unroll
+  for (int w = 1; w < kRowWaves; ++w) v = pick(v, s_rv[w]);
+  __syncthreads();
+  return v;
+}
+__device__ __forceinline__ int32_t row_count(int32_t loc, int tid, int32_t* s_ri) {
+  const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) loc += __shfl_xor(loc, o);
+  if (lane == 0) s_ri[wave] = loc;
+  __syncthreads();
+  int32_t v = 0;
+#pragma unroll
+  for (int w = 0; w < kRowWaves; ++w) v += s_ri[w];
+  __syncthreads();
+  return v;
+}
+
+// The cdf of a histogram of nb <= 4 kRowThreads bins as a fixed-order scan, and the bins nt targets select.
+// Thread t sums its bins 4t .. 4t + 3 in order; the 256 thread sums go through a 64-lane shift scan and the
+// waves in order; cdf(b) = base + (sum of the threads before) + (the thread's own partial up to b).  Target k
+// is s_tgt[k], or with kScale s_tgt[k] = level[k] * total is formed here first.  The bin taken for it is the
+// smallest non-empty b with cdf(b) >= target, or the last non-empty bin when rounding leaves none; s_pick[k]
+// receives it and s_base[k] the cdf before it.  s_pick needs 2 nt entries.  Returns the total (every thread the
+// same value); when it is not > 0 nothing is selected and s_pick / s_base are not to be read.
+template <bool kScale>
+__device__ __forceinline__ double hist_select(const double* h, int nb, double base, const double* level, double* s_tgt,
+                                              int nt, int tid, double* s_rv, int32_t* s_pick, double* s_base,
+                                              int32_t* s_last) {
+  const int lane = tid & 63, wave = tid >> 6, b0 = 4 * tid;
+  double a[4], p[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) a[i] = b0 + i < nb ? h[b0 + i] : 0.0;
+  p[0] = a[0];
+#pragma unroll
+  for (int i = 1; i < 4; ++i) p[i] = p[i - 1] + a[i];
+  double v = p[3];
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double n = __shfl_up(v, o);
+    if (lane >= o) v += n;
+  }
+  double ex = __shfl_up(v, 1);
+  if (lane == 0) ex = 0.0;
+  if (lane == 63) s_rv[wave] = v;
+  if (tid < nt) s_pick[tid] = INT32_MAX;
+  if (tid == 0) *s_last = -1;
+  __syncthreads();
+  double pre = 0.0, total = 0.0;
+#pragma unroll
+  for (int w = 0; w < kRowWaves; ++w) {
+    if (w == wave) pre = total;
+    total += s_rv[w];
+  }
+  if (kScale && tid < nt) s_tgt[tid] = level[tid] * total;
+  if (!(total > 0.0)) {
+    __syncthreads();
+    return total;
+  }
+  if (kScale) __syncthreads();
+  const double off = base + (pre + ex);
+  for (int k = 0; k < nt; ++k) {
+    const double t = s_tgt[k];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (a[i] > 0.0 && off + p[i] >= t) { atomicMin(&s_pick[k], b0 + i); break; }   // integer, LDS
+  }
+#pragma unroll
+  for (int i = 3; i >= 0; --i)
+    if (a[i] > 0.0) { atomicMax(s_last, b0 + i); break; }
+  __syncthreads();
+  for (int k = 0; k < nt; ++k) {
+    int32_t b = s_pick[k];
+    if (b == INT32_MAX) b = *s_last;
+    if ((b >> 2) == tid) {            // total > 0: some bin is non-empty, b >= 0
+      s_pick[nt + k] = b;
+      const int i = b & 3;
+      s_base[k] = i == 0 ? off : off + (i == 1 ? p[0] : i == 2 ? p[1] : p[2]);
+    }
+  }
+  __syncthreads();
+  return total;
+}
+
 // ---- the model posteriors of spectrum q (process.py model_posteriors / model_posteriors_multi /
 // model_posteriors_sub): e[i] = exp(lp_i - max) over the columns no-DLA, DLA levels 1..D, then (sub) the sub-DLA
 // model (n columns), and their sum.  A NaN evidence at a level >= 2 enters as -inf; any other NaN makes every

@@ -197,6 +197,46 @@ class Engine:
                                want_samples, kwargs.get("min_z_separation"), kwargs.get("occam_log_penalty"),
                                kwargs.get("raise_numeric", False), kwargs.get("memory", "host"), summary)
 
+    def process_intervals(self, packed: dict, max_dlas: int, log_nhi_samples, levels=None, lr_delta: float = 2.0,
+                          z_edges=None, log_nhi_edges=None, want_samples: bool = False, **kwargs) -> dict:
+        """``process_summaries`` (same arguments, same outputs bit for bit) with the posterior intervals of
+        every absorber of every level reduced on the device as well (gpdla_engine_process_intervals).
+        ``levels`` are up to 8 quantile levels strictly inside (0, 1), increasing (default
+        ``DEFAULT_INTERVAL_LEVELS``); ``lr_delta`` > 0 the likelihood-ratio depth.  Besides the summaries, with
+        L = len(levels) and slot u of level d its u-th absorber (own first, then the base chain's):
+
+        ``z_dla_quantiles`` / ``log_nhi_quantiles`` (D x Q x D x L)  the smallest slot value whose cumulative
+                                           posterior mass reaches level x total: bitwise a sample value
+        ``z_dla_means`` / ``_sds``, ``log_nhi_means`` / ``_sds`` (D x Q x D)  posterior mean and sd
+        ``z_dla_lr_ranges`` / ``log_nhi_lr_ranges`` (D x Q x D x 2)  min and max over the samples with
+                                           l > max l - lr_delta; ``lr_counts`` (D x Q int32) how many those are
+        ``interval_levels`` (L), ``lr_delta``  the arguments as used
+        Unused slots, and rows without a usable weight sum, are NaN (count 0).  Repeated calls, any
+        ``max_batch_spectra`` and either ``memory`` give bitwise equal results."""
+        if (z_edges is None) != (log_nhi_edges is None):
+            raise ValueError("z_edges and log_nhi_edges go together")
+        lognhi = np.ascontiguousarray(log_nhi_samples, dtype=np.float64).ravel()
+        if lognhi.size != self.num_samples:
+            raise ValueError("one log_nhi sample per engine sample")
+        summary = dict(log_nhi=lognhi,
+                       z_edges=None if z_edges is None else np.ascontiguousarray(z_edges, dtype=np.float64).ravel(),
+                       n_edges=None if log_nhi_edges is None else np.ascontiguousarray(log_nhi_edges, dtype=np.float64).ravel())
+        order = ("resample_uniforms", "base_sample_inds", "min_z_separation", "occam_log_penalty", "raise_numeric", "memory")
+        unknown = set(kwargs) - set(order)
+        if unknown:
+            raise TypeError(f"unexpected keyword arguments {sorted(unknown)}")
+        intervals = dict(log_nhi=lognhi, levels=_interval_levels(levels), lr_delta=float(lr_delta))
+        return self._run_multi(packed, max_dlas, kwargs.get("resample_uniforms"), kwargs.get("base_sample_inds"),
+                               want_samples, kwargs.get("min_z_separation"), kwargs.get("occam_log_penalty"),
+                               kwargs.get("raise_numeric", False), kwargs.get("memory", "host"), summary,
+                               intervals=intervals)
+
+    def interval_stats(self) -> dict:
+        """gpdla_engine_get_interval_stats: cumulative ms and count of the interval launches."""
+        ms, n = C.c_double(0.0), C.c_int64(0)
+        L.check(self.lib.gpdla_engine_get_interval_stats(self._h, C.byref(ms), C.byref(n)))
+        return dict(interval_ms=ms.value, interval_launches=n.value)
+
     def summary_stats(self) -> dict:
         """gpdla_engine_get_summary_stats: cumulative ms and count of the summary launches."""
         ms, n = C.c_double(0.0), C.c_int64(0)
@@ -205,13 +245,15 @@ class Engine:
 
     def _run_multi(self, packed, max_dlas, resample_uniforms, base_sample_inds, want_samples, min_z_separation,
                    occam_log_penalty, raise_numeric, memory, summary, sub=None, models=False, population=None,
-                   levels=None) -> dict:
+                   levels=None, intervals=None) -> dict:
         """process_multi / process_summaries / process_models / process_population: ``summary`` is None or
         the samples' log N_HI and the grid; ``sub`` None or the sub-DLA column densities (``nhi``) and, for the
         MAP outputs, their log10 (``log_nhi``); ``models`` routes the call through gpdla_engine_process_models,
         ``models="population"`` through gpdla_engine_process_population with ``population`` None (both structs
         NULL) or the normalised dict of ``process_population``; ``levels`` (with ``models="population"``) routes
-        it through gpdla_engine_process_levels with the halves it names ("planes", "split")."""
+        it through gpdla_engine_process_levels with the halves it names ("planes", "split"); ``intervals`` (with
+        ``summary`` alone) routes it through gpdla_engine_process_intervals: the samples' log N_HI, ``levels`` and
+        ``lr_delta``."""
         D, S = int(max_dlas), self.num_samples
         offsets = np.ascontiguousarray(packed["offsets"], dtype=np.int64)
         Q = offsets.size - 1
@@ -257,6 +299,31 @@ class Engine:
                         map_z_dlas=np.full((Dc, Q, L.MAX_DLAS), np.nan), map_log_nhis=np.full((Dc, Q, L.MAX_DLAS), np.nan))
             if ez is not None:
                 sout["bin_planes"] = np.zeros((Q, L.SUMMARY_PLANES, max(nz, 0), max(nn, 0)))
+
+        ispec, iout = None, {}
+        if intervals is not None:
+            if spec is None or sub is not None or models or population is not None or levels:
+                raise ValueError("intervals go with the summaries alone")
+            lv_q = intervals["levels"]
+            nlq = min(lv_q.size, L.INTERVAL_MAX_LEVELS)
+            ispec = L.IntervalSpec(log_nhi_samples=L.ptr(intervals["log_nhi"]), lr_delta=intervals["lr_delta"],
+                                   num_levels=lv_q.size)
+            for i in range(nlq):
+                ispec.levels[i] = lv_q[i]
+            slot = (Dc, Q, L.MAX_DLAS)
+            iout = dict(z_dla_means=np.full(slot, np.nan), z_dla_sds=np.full(slot, np.nan),
+                        log_nhi_means=np.full(slot, np.nan), log_nhi_sds=np.full(slot, np.nan),
+                        z_dla_lr_ranges=np.full(slot + (2,), np.nan), log_nhi_lr_ranges=np.full(slot + (2,), np.nan),
+                        z_dla_quantiles=np.full(slot + (max(nlq, 1),), np.nan),
+                        log_nhi_quantiles=np.full(slot + (max(nlq, 1),), np.nan),
+                        lr_counts=np.zeros((Dc, Q), dtype=np.int32))
+
+        def results_intervals(mem, get):
+            return L.Intervals(memory=mem, z_means=get("z_dla_means"), z_sds=get("z_dla_sds"),
+                               log_nhi_means=get("log_nhi_means"), log_nhi_sds=get("log_nhi_sds"),
+                               z_lr_ranges=get("z_dla_lr_ranges"), log_nhi_lr_ranges=get("log_nhi_lr_ranges"),
+                               z_quantiles=get("z_dla_quantiles"), log_nhi_quantiles=get("log_nhi_quantiles"),
+                               lr_counts=get("lr_counts", C.c_int32))
 
         subs, subout = None, {}
         if sub is not None:
@@ -330,7 +397,10 @@ class Engine:
                                 map_log_likelihoods=get("map_log_likelihood_lls"), map_z_lls=get("MAP_z_lls"),
                                 map_log_nhi_lls=get("MAP_log_nhi_lls"))
 
-        def call(sp, rs, sm, rsub=None, rpop=None, rlv=None):
+        def call(sp, rs, sm, rsub=None, rpop=None, rlv=None, riv=None):
+            if ispec is not None:
+                return self.lib.gpdla_engine_process_intervals(self._h, C.byref(sp), C.byref(md), C.byref(rs),
+                                                               C.byref(spec), C.byref(sm), C.byref(ispec), C.byref(riv))
             if levels is not None:
                 return self.lib.gpdla_engine_process_levels(
                     self._h, C.byref(sp), C.byref(md), C.byref(subs) if subs is not None else None, C.byref(rs),
@@ -372,7 +442,9 @@ class Engine:
                                  bin_planes=L.ptr(pl) if pl is not None and pl.size else None)
             rc = call(sp, rs, sm, results_sub(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(subout.get(k), t)),
                       results_pop(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(pout[k], t) if pout[k].size else None),
-                      results_levels(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(lvout[k], t) if k in lvout and lvout[k].size else None))
+                      results_levels(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(lvout[k], t) if k in lvout and lvout[k].size else None),
+                      results_intervals(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(iout[k], t) if iout[k].size else None)
+                      if ispec is not None else None)
         elif memory == "device":
             dev = {k: L.DeviceArray.from_numpy(v, self.device) for k, v in
                    dict(wl=wl, fl=fl, nv=nv, mk=mk, zq=zq).items()}
@@ -403,12 +475,17 @@ class Engine:
             dsub = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in subout.items() if v.size}
             dpop = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in pout.items() if v.size}
             dlv = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in lvout.items() if v.size}
+            div = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in iout.items() if v.size}
             rc = call(sp, rs, sm, results_sub(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dsub[k].ptr, t) if k in dsub else None),
                       results_pop(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dpop[k].ptr, t) if k in dpop else None),
-                      results_levels(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dlv[k].ptr, t) if k in dlv else None))
+                      results_levels(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dlv[k].ptr, t) if k in dlv else None),
+                      results_intervals(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(div[k].ptr, t) if k in div else None)
+                      if ispec is not None else None)
             if rc in (L.GPDLA_OK, L.GPDLA_ENUMERIC):
                 for k, d in dlv.items():
                     lvout[k] = d.numpy()
+                for k, d in div.items():
+                    iout[k] = d.numpy()
                 for k, d in dpop.items():
                     pout[k] = d.numpy()
                 for k, d in dout.items():
@@ -417,7 +494,7 @@ class Engine:
                     sout[k] = d.numpy()
                 for k, d in dsub.items():
                     subout[k] = d.numpy()
-            for d in list(dev.values()) + list(dout.values()) + list(dsum.values()) + list(dsub.values()) + list(dpop.values()) + list(dlv.values()):
+            for d in list(dev.values()) + list(dout.values()) + list(dsum.values()) + list(dsub.values()) + list(dpop.values()) + list(dlv.values()) + list(div.values()):
                 d.free()
         else:
             raise ValueError("memory must be 'host' or 'device'")
@@ -434,6 +511,10 @@ class Engine:
         out.update(subout)
         out.update(pout)
         out.update(lvout)
+        if ispec is not None:
+            for key, v in iout.items():   # the C arrays are GPDLA_MAX_DLAS slots wide
+                out[key] = v if key == "lr_counts" else np.ascontiguousarray(v[:, :, :Dc])
+            out["interval_levels"], out["lr_delta"] = intervals["levels"].copy(), float(intervals["lr_delta"])
         return out
 
     # --------------------------------------------------------------------- sub-DLA model and forest
@@ -702,6 +783,61 @@ def resample(log_likelihoods, uniforms, device: int = 0) -> np.ndarray:
         raise ValueError("one uniform per sample")
     out = np.empty((rows, S), dtype=np.int32)
     L.check(L.load().gpdla_resample_f64(device, L.ptr(ll), rows, S, S, L.ptr(u), L.ptr(out, C.c_int32)))
+    return out
+
+
+DEFAULT_INTERVAL_LEVELS = (0.025, 0.16, 0.5, 0.84, 0.975)
+
+
+def _interval_levels(levels) -> np.ndarray:
+    """The quantile levels as the library takes them (it validates their values and their number)."""
+    lv = np.ascontiguousarray(DEFAULT_INTERVAL_LEVELS if levels is None else levels, dtype=np.float64).ravel()
+    return lv
+
+
+def posterior_intervals(log_likelihoods, offset_samples, log_nhi_samples, min_z, max_z, base_sample_inds=None,
+                        levels=None, lr_delta: float = 2.0, device: int = 0) -> dict:
+    """The interval kernel alone (gpdla_posterior_intervals_f64) on host arrays, with ``posterior_summary``'s
+    inputs: ``log_likelihoods`` rows x S or levels x rows x S, ``base_sample_inds`` (levels - 1) x rows x S.
+    Returns ``Engine.process_intervals``'s interval arrays."""
+    ll = np.ascontiguousarray(log_likelihoods, dtype=np.float64)
+    if ll.ndim == 2:
+        ll = ll[None]
+    if ll.ndim != 3:
+        raise ValueError("log_likelihoods must be rows x S or levels x rows x S")
+    nlv, rows, S = ll.shape
+    off = np.ascontiguousarray(offset_samples, dtype=np.float64).ravel()
+    lognhi = np.ascontiguousarray(log_nhi_samples, dtype=np.float64).ravel()
+    zmin = np.ascontiguousarray(np.broadcast_to(np.asarray(min_z, dtype=np.float64), (rows,)))
+    zmax = np.ascontiguousarray(np.broadcast_to(np.asarray(max_z, dtype=np.float64), (rows,)))
+    if not off.size == lognhi.size == S:
+        raise ValueError("sample arrays must have S entries")
+    base = None
+    if base_sample_inds is not None:
+        base = np.ascontiguousarray(base_sample_inds, dtype=np.int32)
+        if base.shape != (max(nlv - 1, 0), rows, S):
+            raise ValueError(f"base_sample_inds must be {(nlv - 1, rows, S)}")
+    lv = _interval_levels(levels)
+    nlq = min(lv.size, L.INTERVAL_MAX_LEVELS)
+    ispec = L.IntervalSpec(log_nhi_samples=L.ptr(lognhi), lr_delta=float(lr_delta), num_levels=lv.size)
+    for i in range(nlq):
+        ispec.levels[i] = lv[i]
+    Lc = min(max(nlv, 1), L.MAX_DLAS)
+    slot = (nlv, rows, L.MAX_DLAS)
+    o = dict(z_dla_means=np.full(slot, np.nan), z_dla_sds=np.full(slot, np.nan), log_nhi_means=np.full(slot, np.nan),
+             log_nhi_sds=np.full(slot, np.nan), z_dla_lr_ranges=np.full(slot + (2,), np.nan),
+             log_nhi_lr_ranges=np.full(slot + (2,), np.nan), z_dla_quantiles=np.full(slot + (max(nlq, 1),), np.nan),
+             log_nhi_quantiles=np.full(slot + (max(nlq, 1),), np.nan), lr_counts=np.zeros((nlv, rows), dtype=np.int32))
+    iv = L.Intervals(memory=L.MEM_HOST, z_means=L.ptr(o["z_dla_means"]), z_sds=L.ptr(o["z_dla_sds"]),
+                     log_nhi_means=L.ptr(o["log_nhi_means"]), log_nhi_sds=L.ptr(o["log_nhi_sds"]),
+                     z_lr_ranges=L.ptr(o["z_dla_lr_ranges"]), log_nhi_lr_ranges=L.ptr(o["log_nhi_lr_ranges"]),
+                     z_quantiles=L.ptr(o["z_dla_quantiles"]), log_nhi_quantiles=L.ptr(o["log_nhi_quantiles"]),
+                     lr_counts=L.ptr(o["lr_counts"], C.c_int32))
+    L.check(L.load().gpdla_posterior_intervals_f64(
+        device, L.ptr(ll), rows, S, S, L.ptr(off), L.ptr(lognhi), L.ptr(zmin), L.ptr(zmax),
+        L.ptr(base, C.c_int32) if base is not None and base.size else None, nlv, C.byref(ispec), C.byref(iv)))
+    out = {k: (v if k == "lr_counts" else np.ascontiguousarray(v[:, :, :Lc])) for k, v in o.items()}
+    out["interval_levels"], out["lr_delta"] = lv.copy(), float(lr_delta)
     return out
 
 

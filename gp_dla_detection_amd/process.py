@@ -317,7 +317,31 @@ def _model_log_priors(z_qsos, prior: dict | None, params: Parameters, max_dlas: 
     return lp_no, np.ascontiguousarray(np.asarray(lp_dla, dtype=np.float64).T), lp_lls
 
 
-def _compute_kwargs(max_dlas: int, summaries, save_samples: bool, sub=None, forest=None, population=None) -> dict:
+def _interval_spec(intervals):
+    """``intervals`` of process_qsos -> None (off) or dict(levels, lr_delta): True takes the defaults
+    (engine.DEFAULT_INTERVAL_LEVELS, lr_delta = 2).  The levels are up to 8 numbers strictly inside (0, 1),
+    strictly increasing; lr_delta is finite and > 0."""
+    if intervals is None or intervals is False:
+        return None
+    given = {} if intervals is True else intervals
+    if not isinstance(given, dict) or set(given) - {"levels", "lr_delta"}:
+        raise ValueError("intervals must be None, True or dict(levels=..., lr_delta=...)")
+    from .engine import DEFAULT_INTERVAL_LEVELS
+    levels = np.asarray(given.get("levels", DEFAULT_INTERVAL_LEVELS), dtype=np.float64).ravel()
+    lr_delta = float(given.get("lr_delta", 2.0))
+    if not 1 <= levels.size <= 8:
+        raise ValueError("intervals levels: 1 to 8 quantile levels")
+    if not (np.all(levels > 0.0) and np.all(levels < 1.0)):
+        raise ValueError("intervals levels must lie strictly inside (0, 1)")
+    if not np.all(np.diff(levels) > 0.0):
+        raise ValueError("intervals levels must be strictly increasing")
+    if not (np.isfinite(lr_delta) and lr_delta > 0.0):
+        raise ValueError("intervals lr_delta must be finite and > 0")
+    return dict(levels=levels, lr_delta=lr_delta)
+
+
+def _compute_kwargs(max_dlas: int, summaries, save_samples: bool, sub=None, forest=None, population=None,
+                    intervals=None) -> dict:
     """What a ``compute`` replacement is told beyond the five positional arguments: only what differs
     from the plain single-DLA call, so existing replacements keep working.  ``sub_dla`` is the normalised
     dict(nhi, log_nhi, ratio), ``forest`` the full settings dict, ``population`` the normalised dict of
@@ -335,19 +359,22 @@ def _compute_kwargs(max_dlas: int, summaries, save_samples: bool, sub=None, fore
         kw["summaries"] = summaries
     if not save_samples:
         kw["save_samples"] = False
+    if intervals is not None:
+        kw["intervals"] = intervals
     return kw
 
 
 def _engine_compute(model: dict, samples: dict, packed: dict, params: Parameters, device: int = 0,
                     engine: Engine | None = None, max_dlas: int = 1, summaries=None, save_samples: bool = True,
-                    timings: dict | None = None, sub_dla=None, forest=None, population=None) -> dict:
+                    timings: dict | None = None, sub_dla=None, forest=None, population=None, intervals=None) -> dict:
     """The hot path on the GPU: per-spectrum null / sample / DLA log likelihoods and z ranges; with
     ``max_dlas`` > 1 every level of the multi-DLA search (Engine.process_multi's arrays); with
     ``summaries`` the posterior summaries as well (Engine.process_summaries), the sample arrays only if
     ``save_samples``.  ``sub_dla`` (the normalised dict of ``_sub_dla_spec``) adds the sub-DLA model's arrays
     (Engine.process_models); ``forest`` (the settings dict) is set on the engine for this call and cleared
     after it.  ``population`` (the dict ``_compute_kwargs`` documents) adds Engine.process_population's arrays;
-    ``levels="all"`` in either dict routes the call through Engine.process_levels for that half."""
+    ``levels="all"`` in either dict routes the call through Engine.process_levels for that half.  ``intervals``
+    (the dict of ``_interval_spec``; with ``summaries`` alone) adds Engine.process_intervals's arrays."""
     grid = _summary_grid(summaries)
     halves = (("planes",) if _summary_levels(summaries) else ()) + \
              (("split",) if population is not None and population.get("levels") == "all" else ())
@@ -409,8 +436,13 @@ def _engine_compute(model: dict, samples: dict, packed: dict, params: Parameters
         if grid is not None:
             if "log_nhi_samples" not in samples:
                 raise ValueError("summaries need samples['log_nhi_samples']")
-            res = eng.process_summaries(packed, max_dlas, samples["log_nhi_samples"], z_edges=grid[0],
-                                        log_nhi_edges=grid[1], want_samples=save_samples)
+            if intervals is not None:
+                res = eng.process_intervals(packed, max_dlas, samples["log_nhi_samples"], levels=intervals["levels"],
+                                            lr_delta=intervals["lr_delta"], z_edges=grid[0], log_nhi_edges=grid[1],
+                                            want_samples=save_samples)
+            else:
+                res = eng.process_summaries(packed, max_dlas, samples["log_nhi_samples"], z_edges=grid[0],
+                                            log_nhi_edges=grid[1], want_samples=save_samples)
             if max_dlas == 1:   # Engine.process's shapes: no level axis, no multi-DLA variables
                 res["log_likelihoods_dla"] = res["log_likelihoods_dla"][0]
                 if "sample_log_likelihoods_dla" in res:
@@ -489,6 +521,29 @@ def _finish_summaries(out: dict, res: dict, summaries, max_dlas: int) -> dict:
     if grid[0] is not None:
         out["bin_planes"] = np.asarray(res["bin_planes"], dtype=np.float64)
         out["bin_z_edges"], out["bin_log_nhi_edges"] = grid
+    return out
+
+
+def _finish_intervals(out: dict, res: dict, ivs: dict, max_dlas: int) -> dict:
+    """Add INTERVAL_VARIABLES to the saved ones.  ``res`` holds Engine.process_intervals's arrays (D x Q x D
+    [x 2 | x L] per absorber slot, D x Q counts); the saved ones are spectrum-major and 4 slots wide whatever D
+    is: Q x D x 4 [x 2 | x L], unused slots NaN, ``lr_counts`` Q x D doubles."""
+    D, L = int(max_dlas), ivs["levels"].size
+    Q = np.asarray(out["log_likelihoods_no_dla"]).size
+    tails = dict(z_dla_quantiles=(L,), log_nhi_quantiles=(L,), z_dla_means=(), z_dla_sds=(), log_nhi_means=(),
+                 log_nhi_sds=(), z_dla_lr_ranges=(2,), log_nhi_lr_ranges=(2,))
+    for key, tail in tails.items():
+        v = np.asarray(res[key], dtype=np.float64)
+        if v.shape != (D, Q, D) + tail:
+            raise ValueError(f"{key} must be {(D, Q, D) + tail}")
+        wide = np.full((Q, D, 4) + tail, np.nan)
+        wide[:, :, :D] = np.swapaxes(v, 0, 1)
+        out[key] = wide
+    cnt = np.asarray(res["lr_counts"])
+    if cnt.shape != (D, Q):
+        raise ValueError(f"lr_counts must be {(D, Q)}")
+    out["lr_counts"] = np.ascontiguousarray(cnt.T.astype(np.float64))
+    out["interval_levels"], out["lr_delta"] = ivs["levels"].copy(), float(ivs["lr_delta"])
     return out
 
 
@@ -615,7 +670,8 @@ def _finish(res: dict, z_qsos, prior: dict | None, params: Parameters, metadata:
 def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
                  params: Parameters | None = None, test_ind=None, engine: Engine | None = None,
                  device: int = 0, metadata: dict | None = None, max_dlas: int = 1, compute=None,
-                 summaries=None, save_samples: bool = True, sub_dla=None, forest=None, population=None) -> dict:
+                 summaries=None, save_samples: bool = True, sub_dla=None, forest=None, population=None,
+                 intervals=None) -> dict:
     """Run the DLA search (process_qsos.m:88-232) and return the saved variables.  ``max_dlas`` > 1
     (up to 4) runs the multi-DLA search: ``log_likelihoods_dla`` / ``log_priors_dla`` /
     ``log_posteriors_dla`` become Q x D, ``model_posteriors`` Q x (1 + D), ``sample_log_likelihoods_dla``
@@ -662,9 +718,32 @@ def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
     ``population_level_large_bins`` (Q x D x 8 x 4; indices and bins 1-based, 0 = none) --
     LEVEL_POPULATION_VARIABLES, which catalog.py's functions read with ``levels="all"``.  The default
     ``levels="first"`` is the run without the key.  A ``compute`` replacement finds ``levels="all"`` inside the
-    ``summaries`` / ``population`` dicts it already gets."""
+    ``summaries`` / ``population`` dicts it already gets.
+
+    ``intervals`` (True, or ``dict(levels=..., lr_delta=...)``; see ``_interval_spec``) has the engine reduce
+    credible intervals for every absorber of every level (Engine.process_intervals) and
+    adds INTERVAL_VARIABLES: ``z_dla_quantiles`` / ``log_nhi_quantiles`` (Q x D x 4 x L: level d's absorber
+    slot u, own first and then the base chain's, unused slots NaN), ``z_dla_means`` / ``_sds`` and
+    ``log_nhi_means`` / ``_sds`` (Q x D x 4), ``z_dla_lr_ranges`` / ``log_nhi_lr_ranges`` (Q x D x 4 x 2: the
+    reference's find_delta_z / find_delta_NHI are hi - lo of level 1, slot 0), ``lr_counts`` (Q x D),
+    ``interval_levels`` (L) and ``lr_delta``.  It runs with the summaries -- without ``summaries`` it implies
+    ``summaries=True`` (the MAP pairs) -- and composes with ``max_dlas``, a summary grid, ``forest`` and
+    ``save_samples=False``.  With ``population``, ``sub_dla`` or ``levels="all"`` it raises ValueError: those
+    calls do not carry the interval launches (the sub-DLA model has no intervals yet).  Without the keyword
+    every variable is as before, bit for bit.  A ``compute`` replacement receives ``intervals=`` (dict(levels,
+    lr_delta)) when it is set."""
     if not 1 <= int(max_dlas) <= 4:
         raise ValueError("max_dlas must be 1..4")
+    ivs = _interval_spec(intervals)
+    if ivs is not None:
+        if population is not None and population is not False:
+            raise ValueError("intervals do not combine with population: run the population statistics in a call of their own")
+        if sub_dla is not None and sub_dla is not False:
+            raise ValueError("intervals do not combine with sub_dla: the sub-DLA model has no intervals")
+        if _summary_levels(summaries):
+            raise ValueError("intervals do not combine with summaries levels='all'")
+        if _summary_grid(summaries) is None:
+            summaries = True
     pop = _population_spec(population)
     params = params or set_parameters(k=np.asarray(model["M"]).shape[1])
     sub, fst = _sub_dla_spec(sub_dla, samples, device), _forest_spec(forest)
@@ -675,14 +754,16 @@ def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
         popkw = dict(pop, log_priors_no_dla=lp_no, log_priors_dla=lp_dla, log_priors_lls=lp_lls)
     if compute is not None:
         res = compute(model, samples, packed, params, device,
-                      **_compute_kwargs(max_dlas, summaries, save_samples, sub, fst, popkw))
+                      **_compute_kwargs(max_dlas, summaries, save_samples, sub, fst, popkw, ivs))
     else:
         res = _engine_compute(model, samples, packed, params, device, engine, max_dlas, summaries, save_samples,
-                              sub_dla=sub, forest=fst, population=popkw)
+                              sub_dla=sub, forest=fst, population=popkw, intervals=ivs)
     if not save_samples:
         res = {k: v for k, v in res.items() if k not in ("sample_log_likelihoods_dla", "base_sample_inds",
                                                          "sample_log_likelihoods_lls")}
     out = _finish(res, packed["z_qsos"], prior, params, metadata, max_dlas, summaries, sub, fst)
+    if ivs is not None:
+        _finish_intervals(out, res, ivs, max_dlas)
     if pop is not None:
         _finish_population(out, res, pop)
     _finish_levels(out, res, summaries, pop, max_dlas)
@@ -723,6 +804,9 @@ POPULATION_VARIABLES = ("population_poisson", "population_large_inds", "populati
 LEVEL_POPULATION_VARIABLES = ("bin_planes_levels", "population_level_posteriors", "population_level_poisson",
                               "population_level_large_inds", "population_level_large_probs",
                               "population_level_large_bins")
+# what a run with the posterior intervals saves besides (process_qsos(intervals=...)); catalog.py reads them
+INTERVAL_VARIABLES = ("z_dla_quantiles", "log_nhi_quantiles", "interval_levels", "z_dla_means", "z_dla_sds",
+                      "log_nhi_means", "log_nhi_sds", "z_dla_lr_ranges", "log_nhi_lr_ranges", "lr_counts", "lr_delta")
 
 
 def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
@@ -746,11 +830,12 @@ def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
     ``model_posteriors[2]`` still reads "exactly two DLAs", calc_cddf.py:67), one with ``forest`` the
     FOREST_VARIABLES (and, with a ``mean_flux_scope`` other than "mu", MEAN_FLUX_SCOPE_VARIABLES), one
     with ``population`` the POPULATION_VARIABLES, one with ``levels="all"`` the LEVEL_POPULATION_VARIABLES
-    (h5py sees ``bin_planes_levels`` as (nn, nz, 5, D, Q))."""
+    (h5py sees ``bin_planes_levels`` as (nn, nz, 5, D, Q)), one with ``intervals`` the INTERVAL_VARIABLES."""
     mat = {}
     multi = int(np.ravel(out.get("max_dlas", 1))[0]) > 1
     for key in (PROCESSED_VARIABLES + (MULTI_DLA_VARIABLES if multi else ()) + SUMMARY_VARIABLES + SUB_DLA_VARIABLES +
-                FOREST_VARIABLES + MEAN_FLUX_SCOPE_VARIABLES + POPULATION_VARIABLES + LEVEL_POPULATION_VARIABLES):
+                FOREST_VARIABLES + MEAN_FLUX_SCOPE_VARIABLES + POPULATION_VARIABLES + LEVEL_POPULATION_VARIABLES +
+                INTERVAL_VARIABLES):
         if key not in out:
             continue
         v = out[key]

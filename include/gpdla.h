@@ -521,6 +521,81 @@ int gpdla_population_split_levels_f64(int32_t device, const double* ll, int64_t 
                                       const gpdla_population_spec* spec, double* poisson_plane,
                                       int32_t* large_inds, double* large_probs, int32_t* large_bins);
 
+/* ---- Posterior intervals ----------------------------------------------------
+ * Marginal posterior summaries of z_DLA and log N_HI for every absorber of every level: what
+ * DLACatalogue.find_delta_NHI / find_delta_z (CDDF_analysis/calc_cddf.py:872-886) start, for all levels
+ * and with moments and quantiles.  Row q, level d in 1..D, slot u in 0..d-1.  c_u(j) is the chain of
+ * sample j exactly as the MAP pairs form it (c_0 = j, then the base indices); a sample whose chain is
+ * void (a -1 or an index outside [0, S) on the way) contributes to nothing below.  pi_j = w_j / W as in
+ * the summaries.  The slot's values are
+ *   x^z_j = min_z + (max_z - min_z) * offset[c_u(j)]  (product and sum rounded separately),
+ *   x^N_j = log_nhi[c_u(j)].
+ * Per (q, d, u) and parameter:
+ *   lr_ranges   min and max of x over the non-NaN samples with l_j > m - lr_delta (m the row's maximum,
+ *               the difference rounded once, the comparison strict); lr_counts [D][Q] the number of such
+ *               samples.  Exact reductions.  NaN, NaN when there is none.
+ *   means, sds  mean = sum pi x / T, sd = sqrt(sum pi (x - mean)^2 / T), T = sum pi over the valid-chain
+ *               samples; the second sum is a second pass centred on the computed mean.  Every sum is formed
+ *               in the order of W: strided per-thread partials, xor butterfly, waves in order.  NaN when
+ *               T is 0.
+ *   quantiles   per level p in levels[]: the smallest value x* of the slot whose cumulative mass
+ *               F(x*) = sum_{x_j <= x*} pi_j reaches p T_c.  The masses are summed per dense rank of the
+ *               value (equal values share a rank) in sample-index order, first over coarse bins rank >> s
+ *               (s the smallest shift that leaves at most 1,024 bins of S ranks), then over the 2^s ranks
+ *               of the coarse bin each level selects; the cdf is a fixed-order scan of the bins (four bins
+ *               per thread in order, the 256 thread sums by a 64-lane shift scan, the 4 waves in order),
+ *               T_c the coarse scan's total, and the fine scan starts from the coarse scan's partial.  The
+ *               bin taken is the first non-empty one whose cdf reaches the target; if rounding leaves none,
+ *               the last non-empty one (gpdla_resample_f64's rule).  x* is bitwise one of the slot's values.
+ *               NaN when T_c is 0.
+ * A row whose W is 0 or not finite gives NaN everywhere and a count of 0; slots >= d are NaN.  If min_z or
+ * max_z is not finite, or max_z < min_z, the row's z outputs are NaN and the log N_HI outputs are still
+ * computed; min_z == max_z is legal.  offset_samples and log_nhi_samples must be finite.  S <=
+ * GPDLA_INTERVAL_MAX_SAMPLES.  A row's outputs are a function of the row alone: repeated calls, any split
+ * into device batches, host or device results and runs with or without the sample buffers agree bit for
+ * bit. */
+#define GPDLA_INTERVAL_MAX_LEVELS 8
+#define GPDLA_INTERVAL_MAX_SAMPLES (1 << 20)
+typedef struct gpdla_interval_spec {
+  const double* log_nhi_samples;     /* host [S], the samples' log10 N_HI in the caller's order */
+  double lr_delta;                   /* > 0, finite (the reference's 2) */
+  int32_t num_levels;                /* 1..GPDLA_INTERVAL_MAX_LEVELS */
+  double levels[GPDLA_INTERVAL_MAX_LEVELS];  /* strictly inside (0, 1), strictly increasing */
+} gpdla_interval_spec;
+
+typedef struct gpdla_intervals {
+  int32_t memory;                    /* GPDLA_MEM_HOST or GPDLA_MEM_DEVICE */
+  double* z_means;                   /* [D][Q][GPDLA_MAX_DLAS] */
+  double* z_sds;
+  double* log_nhi_means;
+  double* log_nhi_sds;
+  double* z_lr_ranges;               /* [D][Q][GPDLA_MAX_DLAS][2]: min, max */
+  double* log_nhi_lr_ranges;
+  double* z_quantiles;               /* [D][Q][GPDLA_MAX_DLAS][num_levels] */
+  double* log_nhi_quantiles;
+  int32_t* lr_counts;                /* [D][Q] */
+} gpdla_intervals;
+
+/* gpdla_engine_process_summaries with the interval launches after the summary launch of each device batch;
+ * every other result is that call's, bit for bit.  spec's grid stays optional and the sample arrays of
+ * results may be NULL.  GPDLA_EINVAL for a null ispec, intervals or array of either, lr_delta <= 0 or not
+ * finite, num_levels outside 1..GPDLA_INTERVAL_MAX_LEVELS, a level outside (0, 1), levels not strictly
+ * increasing, or more than GPDLA_INTERVAL_MAX_SAMPLES samples. */
+int gpdla_engine_process_intervals(gpdla_engine* engine, const gpdla_spectra* spectra,
+                                   const gpdla_multi_dla* multi, const gpdla_results_multi* results,
+                                   const gpdla_summary_spec* spec, const gpdla_summaries* summaries,
+                                   const gpdla_interval_spec* ispec, const gpdla_intervals* intervals);
+/* Cumulative kernel time (HIP events) and count of the interval launches since create / reset_stats. */
+int gpdla_engine_get_interval_stats(gpdla_engine* engine, double* ms, int64_t* launches);
+/* The interval kernel alone, host buffers, with gpdla_posterior_summary_f64's inputs (ispec's
+ * log_nhi_samples is not read here); outputs as in gpdla_intervals with D = levels, Q = rows, in host
+ * memory. */
+int gpdla_posterior_intervals_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
+                                  const double* offset_samples, const double* log_nhi_samples,
+                                  const double* min_z, const double* max_z, const int32_t* base_inds,
+                                  int32_t levels, const gpdla_interval_spec* ispec,
+                                  const gpdla_intervals* intervals);
+
 /* voigt MEX replacement (voigt.c:253-304).  Host buffers.  out has n_padded - 6 values. */
 int gpdla_voigt_f64(const double* lambdas, int64_t n_padded, double z, double N,
                     int32_t num_lines, double* out);
