@@ -34,6 +34,7 @@ i64p = C.POINTER(C.c_int64)
 u8p = C.POINTER(C.c_uint8)
 i32p = C.POINTER(C.c_int32)
 fp = C.POINTER(C.c_float)
+u32p = C.POINTER(C.c_uint32)
 
 
 class Model(C.Structure):
@@ -167,6 +168,21 @@ class LevelPopulation(C.Structure):
                 ("large_inds", i32p), ("large_probs", dp), ("large_bins", i32p)]
 
 
+class SearchCuts(C.Structure):
+    _fields_ = [("proximity_zone", C.c_double), ("noise_thresh", C.c_double), ("omega_m", C.c_double),
+                ("num_z_bins_summary", C.c_int32), ("z_edges_summary", dp), ("num_z_bins_population", C.c_int32),
+                ("z_edges_population", dp)]
+
+
+class SearchCutResults(C.Structure):
+    _fields_ = [("memory", C.c_int32), ("z_uppers", dp), ("pixel_counts", i32p), ("bitmap_offsets", i64p),
+                ("bitmap_words", u32p), ("path_summary", dp), ("path_population", dp)]
+
+
+class SampleCuts(C.Structure):
+    _fields_ = [("z_uppers", dp), ("pixel_counts", i32p), ("bitmap_offsets", i64p), ("bitmap_words", u32p)]
+
+
 class BootstrapSpec(C.Structure):
     _fields_ = [("seed", C.c_uint64 * 2), ("num_replicas", C.c_int64), ("first_replica", C.c_int64),
                 ("num_strata", C.c_int32), ("stratum_offsets", i64p), ("members", i32p)]
@@ -250,6 +266,19 @@ SIGNATURES = {
     "gpdla_bootstrap_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.POINTER(BootstrapSpec), dp]),
     "gpdla_spectrum_snrs_f32": (C.c_int, [C.c_int32, C.c_int64, i64p, fp, fp, fp, dp, dp, fp]),
     "gpdla_spectrum_snrs_f64": (C.c_int, [C.c_int32, C.c_int64, i64p, dp, dp, dp, dp, dp, dp]),
+    "gpdla_search_cuts_f64": (C.c_int, [C.c_int32, C.c_int64, i64p, dp, dp, dp, dp, C.POINTER(SearchCuts),
+                                        C.POINTER(SearchCutResults)]),
+    "gpdla_engine_process_cuts": (C.c_int, [C.c_void_p, C.POINTER(Spectra), C.POINTER(MultiDla), C.POINTER(SubDla),
+                                            C.POINTER(ResultsMulti), C.POINTER(ResultsSub), C.POINTER(SummarySpec),
+                                            C.POINTER(Summaries), C.POINTER(PopulationSpec), C.POINTER(Population),
+                                            C.POINTER(LevelPopulation), C.POINTER(SearchCuts),
+                                            C.POINTER(SearchCutResults)]),
+    "gpdla_engine_get_cut_stats": (C.c_int, [C.c_void_p, dp, i64p]),
+    "gpdla_level_planes_cut_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp, dp, i32p,
+                                             C.c_int32, C.POINTER(SummarySpec), C.POINTER(SampleCuts), dp]),
+    "gpdla_population_split_levels_cut_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp,
+                                                        i32p, C.c_int32, dp, C.POINTER(PopulationSpec),
+                                                        C.POINTER(SampleCuts), dp, i32p, dp, i32p]),
     "gpdla_count_mixture_f64": (C.c_int, [C.c_int32, dp, i32p, i64p, i64p, C.c_int64, C.c_int64, dp, C.c_int32, i32p, i32p,
                                           dp, dp]),
     "gpdla_count_mixture_tiling": (C.c_int, [i32p, i32p, i32p]),

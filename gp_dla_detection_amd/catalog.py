@@ -291,16 +291,54 @@ def path_length(z_lo: float, z_hi: float, min_z_dlas, max_z_dlas, keep=None, ome
     return math.fsum(absorption_distance(hi, omega_m) - absorption_distance(lo, omega_m))
 
 
+def cut_path_columns(out, grid: str, keep=None, omega_m: float = 0.279):
+    """The per-spectrum path columns a run under the search cuts stored (``process_qsos(cuts=...)``; DESIGN.md
+    section 22) for ``grid`` ("summary": ``cut_path_summary`` on ``bin_z_edges``; "population":
+    ``cut_path_population`` on ``population_z_edges``), Q x (nz + 1) -- each z bin, then the whole extent -- with the
+    rows ``keep`` drops zeroed: what takes ``path_columns``'s place, so that cut planes never meet an uncut path.
+    None for an ``out`` without the cut variables.  ValueError when the run stored no path for the grid, or stored
+    it for another ``omega_m``."""
+    if "cut_z_uppers" not in out:
+        return None
+    key = "cut_path_" + grid
+    if key not in out:
+        raise ValueError(f"the run was cut but holds no {key}: its planes cannot be paired with an uncut path")
+    if "cut_omega_m" in out and float(np.ravel(out["cut_omega_m"])[0]) != float(omega_m):
+        raise ValueError(f"the stored cut path is for omega_m = {float(np.ravel(out['cut_omega_m'])[0])}, not {omega_m}")
+    cols = np.array(out[key], dtype=np.float64)
+    if keep is not None:
+        cols[~np.asarray(keep, dtype=bool).ravel()] = 0.0
+    return cols
+
+
+def _bin_paths(out, grid: str, z_edges, keep, omega_m):
+    """(the path of every bin of ``z_edges``, the path of their whole extent): ``path_length``, or for a run under
+    the search cuts the ``fsum`` of the stored columns of ``grid``."""
+    import math
+    ez = np.asarray(z_edges, dtype=np.float64).ravel()
+    cols = cut_path_columns(out, grid, keep, omega_m)
+    if cols is None:
+        zmin, zmax = out["min_z_dlas"], out["max_z_dlas"]
+        return (np.array([path_length(a, b, zmin, zmax, keep, omega_m) for a, b in zip(ez[:-1], ez[1:])]),
+                path_length(ez[0], ez[-1], zmin, zmax, keep, omega_m))
+    if cols.ndim != 2 or cols.shape[1] != ez.size:
+        raise ValueError(f"cut_path_{grid} must hold {ez.size} columns")
+    sums = np.array([math.fsum(cols[:, c]) for c in range(ez.size)])
+    return sums[:-1], float(sums[-1])
+
+
 def column_density_function(out, keep=None, p_thresh_spec: float = 0.05, omega_m: float = 0.279, device: int = 0,
                             pmf=None, levels: str = "first"):
     """f(N) = n_DLA / dN / dX (calc_cddf.py:440-464) on the population grid of ``out``: the log N_HI bins are
     ``population_log_nhi_edges`` and the redshift range its whole z extent; ``levels="all"`` counts every
     absorber of every multi-DLA level (``split_distributions``).  Returns (bin centres in log N_HI,
-    f(N), its 68 % band [nn x 2], its 95 % band, (lower, upper) bin half-widths in N_HI)."""
+    f(N), its 68 % band [nn x 2], its 95 % band, (lower, upper) bin half-widths in N_HI).  For an ``out`` of a
+    run under the search cuts the path is the stored cut one (``cut_path_columns``), here and in ``line_density``,
+    ``omega_dla``, ``omega_dla_cddf``, ``bootstrap_moments`` and ``sample_errors``."""
     ez = np.asarray(out["population_z_edges"], dtype=np.float64).ravel()
     en = np.asarray(out["population_log_nhi_edges"], dtype=np.float64).ravel()
     n, l68, l95 = confidence_intervals(out, keep, p_thresh_spec, "log_nhi", device, pmf, levels)
-    dX = path_length(ez[0], ez[-1], out["min_z_dlas"], out["max_z_dlas"], keep, omega_m)
+    dX = _bin_paths(out, "population", ez, keep, omega_m)[1]
     dN = 10.0 ** en[1:] - 10.0 ** en[:-1]
     cent = (en[1:] + en[:-1]) / 2.0
     xerrs = (10.0 ** cent - 10.0 ** en[:-1], 10.0 ** en[1:] - 10.0 ** cent)
@@ -315,7 +353,7 @@ def line_density(out, keep=None, p_thresh_spec: float = 0.05, omega_m: float = 0
     (lower, upper) half-widths)."""
     ez = np.asarray(out["population_z_edges"], dtype=np.float64).ravel()
     n, l68, l95 = confidence_intervals(out, keep, p_thresh_spec, "z", device, pmf, levels)
-    dX = np.array([path_length(a, b, out["min_z_dlas"], out["max_z_dlas"], keep, omega_m) for a, b in zip(ez[:-1], ez[1:])])
+    dX = _bin_paths(out, "population", ez, keep, omega_m)[0]
     ii = dX > 0
     cent = (ez[1:] + ez[:-1]) / 2.0
     xerrs = (cent[ii] - ez[:-1][ii], ez[1:][ii] - cent[ii])
@@ -351,7 +389,7 @@ def omega_dla(out, keep=None, p_thresh_spec: float = 0.05, hubble: float = 0.7, 
     else:
         means, variances = cddf_moments(out["bin_planes"], out["p_dlas"], keep, p_thresh_spec, moment=True)
     mean, variance = means.sum(axis=1), variances.sum(axis=1)
-    dX = np.array([path_length(a, b, out["min_z_dlas"], out["max_z_dlas"], keep, omega_m) for a, b in zip(ez[:-1], ez[1:])])
+    dX = _bin_paths(out, "summary", ez, keep, omega_m)[0]
     with np.errstate(divide="ignore", invalid="ignore"):
         conversion = PROTON_MASS_G * (H100_PER_S * hubble) / LIGHT_CM_PER_S / dX / rho_crit()
     return (ez[1:] + ez[:-1]) / 2.0, mean * conversion, np.sqrt(variance) * conversion, ez
@@ -502,7 +540,7 @@ def omega_dla_cddf(out, keep=None, p_thresh_spec: float = 0.05, hubble: float = 
     ez = np.asarray(out["population_z_edges"], dtype=np.float64).ravel()
     en = np.asarray(out["population_log_nhi_edges"], dtype=np.float64).ravel()
     lists, means = split_distributions_grid(out, keep, p_thresh_spec, levels)
-    dX = np.array([path_length(a, b, out["min_z_dlas"], out["max_z_dlas"], keep, omega_m) for a, b in zip(ez[:-1], ez[1:])])
+    dX = _bin_paths(out, "population", ez, keep, omega_m)[0]
     ii = np.flatnonzero(dX > 0)
     mid, l68, l95, _ = total_column_intervals([lists[i] for i in ii], means[ii], en, tail_prob, cells, device, pmf, mixture)
     conversion = PROTON_MASS_G / LIGHT_CM_PER_S * (H100_PER_S * hubble) / rho_crit(hubble)
@@ -610,7 +648,11 @@ def bootstrap_moments(out, replicas: int, seed, keep=None, strata="auto", levels
             raise ValueError("strata must be 'auto', None or (stratum_offsets, members)")
         strata = bootstrap_strata(zmin, zmax)
     so, mem = (np.array([0, Q], dtype=np.int64), np.arange(Q, dtype=np.int32)) if strata is None else strata
-    path = path_columns(out["bin_z_edges"], zmin, zmax, keep, omega_m)
+    path = cut_path_columns(out, "summary", keep, omega_m)
+    if path is None:
+        path = path_columns(out["bin_z_edges"], zmin, zmax, keep, omega_m)
+    elif path.shape != (Q, nz + 1):
+        raise ValueError(f"cut_path_summary must be {(Q, nz + 1)}")
     if sums is not None:
         got = np.asarray(sums(planes=planes, p_dlas=p, level_posteriors=P, keep=keep, p_thresh_spec=p_thresh_spec, path=path,
                               replicas=replicas, first_replica=first_replica, seed=seed, stratum_offsets=so, members=mem),
@@ -644,8 +686,8 @@ def sample_errors(out, replicas: int = 1000, seed=0, keep=None, strata="auto", l
     import warnings
     bm = bootstrap_moments(out, replicas, seed, keep, strata, levels, device, sums, p_thresh_spec, omega_m)
     ez = np.asarray(out["bin_z_edges"], dtype=np.float64).ravel()
-    zmin, zmax = _first_column(out["min_z_dlas"]), _first_column(out["max_z_dlas"])
-    full = np.array([path_length(a, b, zmin, zmax, keep, omega_m) for a, b in zip(ez[:-1], ez[1:])])
+    full = _bin_paths(dict(out, min_z_dlas=_first_column(out["min_z_dlas"]), max_z_dlas=_first_column(out["max_z_dlas"])),
+                      "summary", ez, keep, omega_m)[0]
     ii = full > 0
     with np.errstate(divide="ignore", invalid="ignore"):
         dX = np.where(bm["path"] > 0, bm["path"], np.nan)
@@ -661,6 +703,28 @@ def sample_errors(out, replicas: int = 1000, seed=0, keep=None, strata="auto", l
             res[f"{name}_95"] = np.array((np.nanpercentile(v, 100 - 5 / 2, axis=0), np.nanpercentile(v, 5 / 2, axis=0)))
             res[f"{name}_replicas"] = v
     return res
+
+
+def search_cuts(preloaded, out, z_edges=None, proximity_zone=0.1, noise_thresh=None, population_z_edges=None,
+                omega_m: float = 0.279, device: int = 0) -> dict:
+    """``lowzcut`` / ``filter_noisy_pixels`` of every searched spectrum on the device, stand-alone
+    (``engine.search_cuts``), in the manner of ``compute_snrs``: ``preloaded`` holds the cells
+    ``all_wavelengths`` and ``all_noise_variance`` (converted to float64), ``out`` the ``min_z_dlas`` /
+    ``max_z_dlas`` of the searched spectra and, when the cells cover the whole catalogue, ``test_ind``.
+    ``z_edges`` / ``population_z_edges`` ask for the path columns of a summary / population grid.  Returns
+    ``engine.search_cuts``'s dict."""
+    from .engine import search_cuts as device_search_cuts
+    zmin, zmax = _first_column(out["min_z_dlas"]), _first_column(out["max_z_dlas"])
+    cells = [list(preloaded[k]) for k in ("all_wavelengths", "all_noise_variance")]
+    if "test_ind" in out and len(cells[0]) != zmax.size:
+        ti = np.asarray(out["test_ind"]).ravel()
+        sel = np.flatnonzero(ti) if ti.dtype == bool else ti.astype(np.int64)
+        cells = [[c[i] for i in sel] for c in cells]
+    if len(cells[0]) != zmax.size:
+        raise ValueError("the preloaded cells and max_z_dlas disagree on the number of spectra")
+    cells = [[np.asarray(c, dtype=np.float64).ravel() for c in lst] for lst in cells]
+    return device_search_cuts(cells[0], cells[1], zmin, zmax, proximity_zone, noise_thresh, z_edges, population_z_edges,
+                              omega_m, device)
 
 
 def compute_snrs(preloaded, out, device: int = 0) -> np.ndarray:

@@ -101,7 +101,7 @@ struct TimedLaunch {
              // 7 posterior summaries (gpdla_engine_process_summaries); 8 forest kernels; gpdla_engine_process_models
              // only: 9 sub-DLA sweep, 10 its log-mean-exp and MAP launches; 11 population launches
              // (gpdla_engine_process_population); 12 level-population launches (gpdla_engine_process_levels);
-             // 13 posterior intervals (gpdla_engine_process_intervals)
+             // 13 posterior intervals (gpdla_engine_process_intervals); 14 search cuts (gpdla_engine_process_cuts)
   int level; // multi-DLA level the span also counts for in gpdla_multi_stats (0: none)
 };
 
@@ -254,6 +254,15 @@ struct gpdla_engine {
   size_t cap_i_lognhi = 0, cap_i_uniq = 0, cap_i_out = 0, cap_i_rank = 0, cap_i_count = 0;
   double interval_ms = 0.0;
   int64_t interval_launches = 0;
+  // search cuts (gpdla_engine_process_cuts): a batch's upper ends, pixel counts, bitmap (the word offsets are those
+  // of the whole call) and path columns, and the call's z edges [summary | population]
+  double *d_c_zu = nullptr, *d_c_path[2] = {nullptr, nullptr}, *d_c_edges = nullptr;
+  int32_t* d_c_np = nullptr;
+  int64_t* d_c_wo = nullptr;
+  uint32_t* d_c_words = nullptr;
+  size_t cap_c_zu = 0, cap_c_path[2] = {0, 0}, cap_c_edges = 0, cap_c_np = 0, cap_c_wo = 0, cap_c_words = 0;
+  double cut_ms = 0.0;
+  int64_t cut_launches = 0;
 
   std::vector<TimedLaunch> pending;
   gpdla_stats stats{};
@@ -287,6 +296,7 @@ int resolve_events(gpdla_engine* e) {
     if (t.kind == 11) { e->population_ms += ms; e->population_launches++; }
     if (t.kind == 12) { e->level_population_ms += ms; e->level_population_launches++; }
     if (t.kind == 13) { e->interval_ms += ms; e->interval_launches++; }
+    if (t.kind == 14) { e->cut_ms += ms; e->cut_launches++; }
     if (t.level >= 1 && t.level <= GPDLA_MAX_DLAS) {
       e->mstats.level_ms[t.level - 1] += ms;
       e->mstats.level_launches[t.level - 1]++;
@@ -395,7 +405,8 @@ void gpdla_engine_destroy(gpdla_engine* e) {
                   e->d_sub_mn, e->d_sub_mind, e->d_p_lpno, e->d_p_lpdla, e->d_p_lplls, e->d_p_lognhi, e->d_p_edges,
                   e->d_p_pdla, e->d_p_plane, e->d_p_lprob, e->d_p_lind, e->d_p_lbin,
                   e->d_lv_post, e->d_lv_planes, e->d_lv_plane, e->d_lv_lprob, e->d_lv_lind, e->d_lv_lbin,
-                  e->d_i_lognhi, e->d_i_uniq, e->d_i_out, e->d_i_rank, e->d_i_count};
+                  e->d_i_lognhi, e->d_i_uniq, e->d_i_out, e->d_i_rank, e->d_i_count,
+                  e->d_c_zu, e->d_c_path[0], e->d_c_path[1], e->d_c_edges, e->d_c_np, e->d_c_wo, e->d_c_words};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (e->h_meta) (void)hipHostFree(e->h_meta);
@@ -1114,6 +1125,8 @@ int gpdla_engine_reset_stats(gpdla_engine* e) {
   e->level_population_launches = 0;
   e->interval_ms = 0.0;
   e->interval_launches = 0;
+  e->cut_ms = 0.0;
+  e->cut_launches = 0;
   e->model_stats = gpdla_model_stats{};
   return GPDLA_OK;
 }
@@ -1178,13 +1191,29 @@ static int validate_summary_grid(const gpdla_summary_spec* spec) {
 // run per batch after the last level, on the batch's evidences and level-1 rows.
 // With lv (gpdla_engine_process_levels) the launches of level_population.hip follow them, on every level's
 // rows and base indices: the planes when spec has a grid, the posteriors and the split when pspec is given.
+// With cuts / cres (gpdla_engine_process_cuts) the search-cut launch runs per batch once its search ranges
+// exist and before the first grid reduction, which then all apply the cuts' sample tests.
 static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
                               const gpdla_results_multi* res, const gpdla_summary_spec* spec,
                               const gpdla_summaries* sums, const gpdla_sub_dla* sub = nullptr,
                               const gpdla_results_sub* rsub = nullptr, const gpdla_population_spec* pspec = nullptr,
                               const gpdla_population* pop = nullptr, const gpdla_level_population* lv = nullptr,
-                              const gpdla_interval_spec* ispec = nullptr, const gpdla_intervals* iv = nullptr) {
+                              const gpdla_interval_spec* ispec = nullptr, const gpdla_intervals* iv = nullptr,
+                              const gpdla_search_cuts* cuts = nullptr, const gpdla_search_cut_results* cres = nullptr) {
   if (!e || !sp || !mu || !res) return set_error(GPDLA_EINVAL, "null argument");
+  if (cuts) {   // (gpdla_engine_process_cuts: cres is set)
+    if (!cres->z_uppers || !cres->pixel_counts || !cres->bitmap_offsets || !cres->bitmap_words)
+      return set_error(GPDLA_EINVAL, "search cuts: null result array");
+    if (cres->memory != GPDLA_MEM_HOST && cres->memory != GPDLA_MEM_DEVICE)
+      return set_error(GPDLA_EINVAL, "search cuts: results memory=%d", cres->memory);
+    int rcc = validate_search_cuts(cuts, cres->path_summary, cres->path_population);
+    if (rcc) return rcc;
+    if (!(spec && spec->num_z_bins > 0) && !pspec)
+      return set_error(GPDLA_EINVAL, "search cuts: no summary or population grid to cut");
+    if (sub) return set_error(GPDLA_EUNSUPPORTED, "search cuts: the sub-DLA model is not covered");
+    if (e->gemm || e->i8)
+      return set_error(GPDLA_EUNSUPPORTED, "the search cuts need the fused fp64 path (this engine runs a panel-GEMM or int8 path)");
+  }
   if (ispec) {   // (gpdla_engine_process_intervals: iv is set)
     if (!ispec->log_nhi_samples) return set_error(GPDLA_EINVAL, "null interval log_nhi_samples");
     if (!iv->z_means || !iv->z_sds || !iv->log_nhi_means || !iv->log_nhi_sds || !iv->z_lr_ranges || !iv->log_nhi_lr_ranges ||
@@ -1339,6 +1368,31 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
       HIP_TRY(hipMemcpyAsync(e->d_p_lplls, pspec->log_priors_lls, Qs * 8, hipMemcpyHostToDevice, st));
     }
   }
+  // search cuts: the bitmap's word offsets over the whole call, and the edges of the path grids
+  std::vector<int64_t> cut_woff;
+  const int cnz[2] = {cuts ? cuts->num_z_bins_summary : 0, cuts ? cuts->num_z_bins_population : 0};
+  if (cuts) {
+    cut_woff.assign((size_t)Q + 1, 0);
+    for (int64_t q = 0; q < Q; ++q) {
+      const int64_t len = sp->offsets[q + 1] - sp->offsets[q];
+      if (len < 0 || len > INT32_MAX - 64) return set_error(GPDLA_EINVAL, "offsets not monotone at %lld", (long long)q);
+      cut_woff[q + 1] = cut_woff[q] + (len + 31) / 32;
+    }
+    if (cres->memory == GPDLA_MEM_DEVICE)
+      HIP_TRY(hipMemcpyAsync(cres->bitmap_offsets, cut_woff.data(), (size_t)(Q + 1) * 8, hipMemcpyHostToDevice, st));
+    else
+      std::memcpy(cres->bitmap_offsets, cut_woff.data(), (size_t)(Q + 1) * 8);
+    // the call-wide offsets go to the device once; cut_woff is not written again before the call's last sync
+    if ((rc = grow(&e->d_c_wo, &e->cap_c_wo, (size_t)Q + 1))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_c_wo, cut_woff.data(), (size_t)(Q + 1) * 8, hipMemcpyHostToDevice, st));
+    if (cnz[0] + cnz[1] > 0) {
+      if ((rc = grow(&e->d_c_edges, &e->cap_c_edges, (size_t)(cnz[0] + cnz[1] + 2)))) return rc;
+      if (cnz[0]) HIP_TRY(hipMemcpyAsync(e->d_c_edges, cuts->z_edges_summary, (size_t)(cnz[0] + 1) * 8, hipMemcpyHostToDevice, st));
+      if (cnz[1])
+        HIP_TRY(hipMemcpyAsync(e->d_c_edges + cnz[0] + 1, cuts->z_edges_population, (size_t)(cnz[1] + 1) * 8,
+                               hipMemcpyHostToDevice, st));
+    }
+  }
   const bool out_dev = res->memory == GPDLA_MEM_DEVICE;
   const hipMemcpyKind out_kind = out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   const bool forced = D > 1 && mu->forced_base_inds;
@@ -1485,6 +1539,48 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
     rows_b.rows = (int32_t)nq; rows_b.levels = D; rows_b.ll = e->d_m_sll; rows_b.ld = S; rows_b.S = S;
     rows_b.base = D > 1 ? e->d_m_base : nullptr; rows_b.ld_base = S;
     rows_b.offset = e->d_off_c; rows_b.zmin = e->d_m_zmin; rows_b.zmax = e->d_m_zmax;
+    if (cuts) {
+      // the cut launch on the batch's resident pixels (the copies gpdla_engine_process made, or the caller's
+      // device arrays) and search ranges; the reductions below read its upper ends and bitmap
+      const int64_t nwb = cut_woff[q0 + nq] - cut_woff[q0];
+      if ((rc = grow(&e->d_c_zu, &e->cap_c_zu, (size_t)nq))) return rc;
+      if ((rc = grow(&e->d_c_np, &e->cap_c_np, (size_t)nq))) return rc;
+      if ((rc = grow(&e->d_c_words, &e->cap_c_words, (size_t)std::max<int64_t>(nwb, 1)))) return rc;
+      for (int g = 0; g < 2; ++g)
+        if (cnz[g] && (rc = grow(&e->d_c_path[g], &e->cap_c_path[g], (size_t)nq * (cnz[g] + 1)))) return rc;
+      // the batch's rows index the call-wide offsets from q0; the words pointer is moved back by the batch's
+      // first word, so offset[q0 + i] lands inside d_c_words
+      const int64_t* batch_wo = e->d_c_wo + q0;
+      uint32_t* batch_words = e->d_c_words - cut_woff[q0];
+      const bool in_dev = sp->memory == GPDLA_MEM_DEVICE;
+      SearchCutArgs ca{};
+      ca.offsets = e->d_meta;   // the batch's pixel offsets, relative to its first pixel
+      ca.wavelengths = in_dev ? sp->wavelengths + sp->offsets[q0] : e->d_wl;
+      ca.noise = in_dev ? sp->noise_variance + sp->offsets[q0] : e->d_noise;
+      ca.zmin = e->d_m_zmin; ca.zmax = e->d_m_zmax;
+      ca.proximity_zone = cuts->proximity_zone; ca.noise_thresh = cuts->noise_thresh; ca.omega_m = cuts->omega_m;
+      ca.word_off = batch_wo; ca.words = batch_words; ca.npix = e->d_c_np; ca.z_upper = e->d_c_zu;
+      ca.nz[0] = cnz[0]; ca.nz[1] = cnz[1];
+      ca.z_edges[0] = e->d_c_edges; ca.z_edges[1] = e->d_c_edges ? e->d_c_edges + cnz[0] + 1 : nullptr;
+      ca.path[0] = e->d_c_path[0]; ca.path[1] = e->d_c_path[1];
+      TimedLaunch t14{};
+      if ((rc = record_start(e, &t14, 14))) return rc;
+      HIP_TRY(launch_search_cuts(ca, nq, st));
+      HIP_TRY(hipEventRecord(t14.stop, st));
+      e->pending.push_back(t14);
+      if (cuts->proximity_zone == cuts->proximity_zone) rows_b.cut_z_upper = e->d_c_zu;
+      if (cuts->noise_thresh == cuts->noise_thresh) {
+        rows_b.cut_npix = e->d_c_np; rows_b.cut_word_off = batch_wo; rows_b.cut_words = batch_words;
+      }
+      const hipMemcpyKind ck = cres->memory == GPDLA_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+      HIP_TRY(hipMemcpyAsync(cres->z_uppers + q0, e->d_c_zu, nq * 8, ck, st));
+      HIP_TRY(hipMemcpyAsync(cres->pixel_counts + q0, e->d_c_np, nq * 4, ck, st));
+      if (nwb) HIP_TRY(hipMemcpyAsync(cres->bitmap_words + cut_woff[q0], e->d_c_words, (size_t)nwb * 4, ck, st));
+      double* cpaths[2] = {cres->path_summary, cres->path_population};
+      for (int g = 0; g < 2; ++g)
+        if (cnz[g])
+          HIP_TRY(hipMemcpyAsync(cpaths[g] + (size_t)q0 * (cnz[g] + 1), e->d_c_path[g], (size_t)nq * (cnz[g] + 1) * 8, ck, st));
+    }
     auto on_grid = [&](const double* log_nhi, int nz, int nn, const double* edges) {
       SampleRowsArgs r = rows_b;
       r.log_nhi = log_nhi; r.nz = nz; r.nn = nn; r.z_edges = edges; r.n_edges = nz ? edges + nz + 1 : nullptr;
@@ -1714,6 +1810,31 @@ int gpdla_engine_process_levels(gpdla_engine* e, const gpdla_spectra* sp, const 
   if (sub && !rsub) return set_error(GPDLA_EINVAL, "null sub-DLA results");
   if ((pspec == nullptr) != (pop == nullptr)) return set_error(GPDLA_EINVAL, "population spec and outputs go together");
   return process_multi_impl(e, sp, mu, res, spec, spec ? sums : nullptr, sub, sub ? rsub : nullptr, pspec, pop, lv);
+}
+
+int gpdla_engine_process_cuts(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
+                              const gpdla_sub_dla* sub, const gpdla_results_multi* res,
+                              const gpdla_results_sub* rsub, const gpdla_summary_spec* spec,
+                              const gpdla_summaries* sums, const gpdla_population_spec* pspec,
+                              const gpdla_population* pop, const gpdla_level_population* lv,
+                              const gpdla_search_cuts* cuts, const gpdla_search_cut_results* cres) {
+  if (spec && !sums) return set_error(GPDLA_EINVAL, "null argument");
+  if (sub && !rsub) return set_error(GPDLA_EINVAL, "null sub-DLA results");
+  if ((pspec == nullptr) != (pop == nullptr)) return set_error(GPDLA_EINVAL, "population spec and outputs go together");
+  if ((cuts == nullptr) != (cres == nullptr)) return set_error(GPDLA_EINVAL, "search cuts: spec and results go together");
+  return process_multi_impl(e, sp, mu, res, spec, spec ? sums : nullptr, sub, sub ? rsub : nullptr, pspec, pop, lv, nullptr,
+                            nullptr, cuts, cres);
+}
+
+int gpdla_engine_get_cut_stats(gpdla_engine* e, double* ms, int64_t* launches) {
+  if (!e || !ms || !launches) return set_error(GPDLA_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  int rc = resolve_events(e);
+  if (rc) return rc;
+  *ms = e->cut_ms;
+  *launches = e->cut_launches;
+  return GPDLA_OK;
 }
 
 int gpdla_engine_get_level_population_stats(gpdla_engine* e, double* ms, int64_t* launches) {

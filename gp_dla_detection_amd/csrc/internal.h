@@ -536,6 +536,12 @@ struct SampleRowsArgs {
   int32_t nz, nn;                // grid (ignored by a summary without planes)
   const double* z_edges;         // device [nz + 1]
   const double* n_edges;         // device [nn + 1]
+  // search cuts (search_cuts.hip), all device arrays; both tests off when the pointers
+  // are null, and the launch then gives the outputs of a launch without these fields bit for bit
+  const double* cut_z_upper;     // [rows], or nullptr: no proximity test (a slot needs z < cut_z_upper[row])
+  const int32_t* cut_npix;       // [rows], or nullptr: no pixel test
+  const int64_t* cut_word_off;   // [rows + 1] with cut_npix: the row's first word of cut_words
+  const uint32_t* cut_words;     // bit i of a row's stretch set: pixel i is good
 };
 // the launch functions' check of the rows, and with `grid` of the bin counts
 inline bool sample_rows_ok(const SampleRowsArgs& r, bool grid = true) {
@@ -641,6 +647,27 @@ hipError_t launch_level_split(const LevelSplitArgs& a, hipStream_t s);
 int validate_grid_edges(const char* prefix, int64_t nz, int64_t nn, const double* z_edges, const double* n_edges);
 int validate_population_grid(int64_t nz, int64_t nn, const double* z_edges, const double* n_edges,
                              double p_thresh_sample, double p_switch);
+
+// ---- search cuts (search_cuts.hip): one workgroup per spectrum
+struct SearchCutArgs {
+  const int64_t* offsets;        // device [Q + 1]
+  const double* wavelengths;
+  const double* noise;
+  const double* zmin;            // [Q]
+  const double* zmax;            // [Q]
+  double proximity_zone, noise_thresh;   // NaN: off
+  double omega_m;
+  int32_t nz[2];                 // summary, population; 0: no grid
+  const double* z_edges[2];      // device [nz + 1]
+  const int64_t* word_off;       // device [Q + 1]
+  uint32_t* words;
+  int32_t* npix;                 // [Q]
+  double* z_upper;               // [Q]
+  double* path[2];               // [Q][nz + 1]
+};
+hipError_t launch_search_cuts(const SearchCutArgs& a, int64_t Q, hipStream_t s);
+// GPDLA_EINVAL with a message unless the thresholds, the grids (each with its path array) and omega_m are usable
+int validate_search_cuts(const struct gpdla_search_cuts* cuts, const double* path_summary, const double* path_population);
 
 // ---- host staging of the stand-alone entry points: one device allocation carved in 256-byte steps, freed
 // when the call returns

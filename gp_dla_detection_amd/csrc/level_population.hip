@@ -103,19 +103,66 @@ hipError_t launch_level_split(const LevelSplitArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// The host arrays of gpdla_sample_cuts behind the cut fields of SampleRowsArgs: check() before the device is
+// touched, carve() before alloc(), upload() after HostSampleRows::upload (which clears the fields)
+struct HostSampleCuts {
+  const gpdla_sample_cuts* c;
+  int64_t rows;
+  size_t o_zu = 0, o_np = 0, o_wo = 0, o_w = 0;
+  int check() const {
+    if (!c) return GPDLA_OK;
+    if (!c->z_uppers && !c->pixel_counts) return set_error(GPDLA_EINVAL, "cuts: neither test is on");
+    if (!c->pixel_counts) return GPDLA_OK;
+    if (!c->bitmap_offsets || (c->bitmap_offsets[rows] > 0 && !c->bitmap_words) || c->bitmap_offsets[0] != 0)
+      return set_error(GPDLA_EINVAL, "cuts: pixel_counts needs the bitmap, its offsets starting at 0");
+    for (int64_t r = 0; r < rows; ++r) {
+      const int64_t w = c->bitmap_offsets[r + 1] - c->bitmap_offsets[r];
+      if (w < 0 || w > INT32_MAX / 32 || c->pixel_counts[r] < 0 || c->pixel_counts[r] > 32 * w)
+        return set_error(GPDLA_EINVAL, "cuts: row %lld has %d pixels in %lld bitmap words", (long long)r, c->pixel_counts[r],
+                         (long long)w);
+    }
+    return GPDLA_OK;
+  }
+  void carve(DeviceStage& st) {
+    if (!c) return;
+    const size_t R = (size_t)rows;
+    o_zu = st.carve(c->z_uppers ? R * 8 : 0);
+    if (c->pixel_counts) { o_np = st.carve(R * 4); o_wo = st.carve((R + 1) * 8); o_w = st.carve((size_t)c->bitmap_offsets[rows] * 4); }
+  }
+  hipError_t upload(DeviceStage& st, SampleRowsArgs* r) const {
+    if (!c) return hipSuccess;
+    const size_t R = (size_t)rows;
+    if (c->z_uppers) {
+      if (hipError_t e = st.upload(o_zu, c->z_uppers, R * 8)) return e;
+      r->cut_z_upper = st.ptr<const double>(o_zu);
+    }
+    if (c->pixel_counts) {
+      const size_t NW = (size_t)c->bitmap_offsets[rows];
+      if (hipError_t e = st.upload(o_np, c->pixel_counts, R * 4)) return e;
+      if (hipError_t e = st.upload(o_wo, c->bitmap_offsets, (R + 1) * 8)) return e;
+      if (NW)
+        if (hipError_t e = st.upload(o_w, c->bitmap_words, NW * 4)) return e;
+      r->cut_npix = st.ptr<const int32_t>(o_np); r->cut_word_off = st.ptr<const int64_t>(o_wo);
+      r->cut_words = st.ptr<const uint32_t>(o_w);
+    }
+    return hipSuccess;
+  }
+};
+
 }  // namespace gpdla
 
 using namespace gpdla;
 
-extern "C" {
 
-int gpdla_level_planes_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
-                           const double* offset_samples, const double* log_nhi_samples, const double* nhi_samples,
-                           const double* min_z, const double* max_z, const int32_t* base_inds, int32_t levels,
-                           const gpdla_summary_spec* spec, double* bin_planes) {
+static int level_planes_host(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
+                             const double* offset_samples, const double* log_nhi_samples, const double* nhi_samples,
+                             const double* min_z, const double* max_z, const int32_t* base_inds, int32_t levels,
+                             const gpdla_summary_spec* spec, const gpdla_sample_cuts* cuts, double* bin_planes) {
   HostSampleRows h{ll, rows, S, ld, offset_samples, log_nhi_samples, nhi_samples, min_z, max_z, base_inds, levels};
   int rc = h.check(true);
   if (rc) return rc;
+  HostSampleCuts hc{cuts, rows};
+  if ((rc = hc.check())) return rc;
   if (!nhi_samples || !spec || !bin_planes) return set_error(GPDLA_EINVAL, "null argument");
   // the edge rules of both grids are the same; the thresholds here are placeholders that always pass
   if ((rc = validate_population_grid(spec->num_z_bins, spec->num_nhi_bins, spec->z_edges, spec->log_nhi_edges, 0.0, 1.0)))
@@ -127,25 +174,29 @@ int gpdla_level_planes_f64(int32_t device, const double* ll, int64_t rows, int64
   const size_t planes_bytes = (size_t)rows * levels * kSummaryPlanes * h.nz * h.nn * 8;
   DeviceStage st;
   h.carve(st);
+  hc.carve(st);
   const size_t o_pl = st.carve(planes_bytes);
   LevelPlanesArgs a{};
   HIP_TRY_IN("level population", st.alloc());
   HIP_TRY_IN("level population", h.upload(st, &a.r, &a.nhi));
+  HIP_TRY_IN("level population", hc.upload(st, &a.r));
   a.planes = st.ptr<double>(o_pl);
   HIP_TRY_IN("level population", launch_level_planes(a, nullptr));
   HIP_TRY_IN("level population", st.download(bin_planes, o_pl, planes_bytes));
   return GPDLA_OK;
 }
 
-int gpdla_population_split_levels_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
-                                      const double* offset_samples, const double* log_nhi_samples,
-                                      const double* min_z, const double* max_z, const int32_t* base_inds,
-                                      int32_t levels, const double* level_posteriors,
-                                      const gpdla_population_spec* spec, double* poisson_plane,
-                                      int32_t* large_inds, double* large_probs, int32_t* large_bins) {
+static int level_split_host(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
+                            const double* offset_samples, const double* log_nhi_samples,
+                            const double* min_z, const double* max_z, const int32_t* base_inds,
+                            int32_t levels, const double* level_posteriors,
+                            const gpdla_population_spec* spec, const gpdla_sample_cuts* cuts, double* poisson_plane,
+                            int32_t* large_inds, double* large_probs, int32_t* large_bins) {
   HostSampleRows h{ll, rows, S, ld, offset_samples, log_nhi_samples, nullptr, min_z, max_z, base_inds, levels};
   int rc = h.check(true);
   if (rc) return rc;
+  HostSampleCuts hc{cuts, rows};
+  if ((rc = hc.check())) return rc;
   if (!level_posteriors || !spec || !poisson_plane || !large_inds || !large_probs || !large_bins)
     return set_error(GPDLA_EINVAL, "null argument");
   if ((rc = validate_population_grid(spec->num_z_bins, spec->num_nhi_bins, spec->z_edges, spec->log_nhi_edges,
@@ -163,11 +214,13 @@ int gpdla_population_split_levels_f64(int32_t device, const double* ll, int64_t 
   const size_t RL = (size_t)rows * levels, nbins = (size_t)h.nz * h.nn, NL = GPDLA_POPULATION_MAX_LARGE;
   DeviceStage st;
   h.carve(st);
+  hc.carve(st);
   const size_t o_P = st.carve(RL * 8), o_pl = st.carve(RL * nbins * 8), o_li = st.carve(RL * NL * 4);
   const size_t o_lp = st.carve(RL * NL * 8), o_lb = st.carve(RL * NL * kMaxDlas * 4);
   LevelSplitArgs a{};
   HIP_TRY_IN("level population", st.alloc());
   HIP_TRY_IN("level population", h.upload(st, &a.r, nullptr));
+  HIP_TRY_IN("level population", hc.upload(st, &a.r));
   HIP_TRY_IN("level population", st.upload(o_P, level_posteriors, RL * 8));
   a.level_post = st.ptr<const double>(o_P); a.ld_post = rows;
   a.p_thresh_sample = spec->p_thresh_sample; a.p_switch = spec->p_switch;
@@ -179,6 +232,45 @@ int gpdla_population_split_levels_f64(int32_t device, const double* ll, int64_t 
   HIP_TRY_IN("level population", st.download(large_probs, o_lp, RL * NL * 8));
   HIP_TRY_IN("level population", st.download(large_bins, o_lb, RL * NL * kMaxDlas * 4));
   return GPDLA_OK;
+}
+
+extern "C" {
+
+int gpdla_level_planes_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
+                           const double* offset_samples, const double* log_nhi_samples, const double* nhi_samples,
+                           const double* min_z, const double* max_z, const int32_t* base_inds, int32_t levels,
+                           const gpdla_summary_spec* spec, double* bin_planes) {
+  return level_planes_host(device, ll, rows, S, ld, offset_samples, log_nhi_samples, nhi_samples, min_z, max_z, base_inds,
+                           levels, spec, nullptr, bin_planes);
+}
+
+int gpdla_level_planes_cut_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
+                               const double* offset_samples, const double* log_nhi_samples, const double* nhi_samples,
+                               const double* min_z, const double* max_z, const int32_t* base_inds, int32_t levels,
+                               const gpdla_summary_spec* spec, const gpdla_sample_cuts* cuts, double* bin_planes) {
+  return level_planes_host(device, ll, rows, S, ld, offset_samples, log_nhi_samples, nhi_samples, min_z, max_z, base_inds,
+                           levels, spec, cuts, bin_planes);
+}
+
+int gpdla_population_split_levels_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
+                                      const double* offset_samples, const double* log_nhi_samples,
+                                      const double* min_z, const double* max_z, const int32_t* base_inds,
+                                      int32_t levels, const double* level_posteriors,
+                                      const gpdla_population_spec* spec, double* poisson_plane,
+                                      int32_t* large_inds, double* large_probs, int32_t* large_bins) {
+  return level_split_host(device, ll, rows, S, ld, offset_samples, log_nhi_samples, min_z, max_z, base_inds, levels,
+                          level_posteriors, spec, nullptr, poisson_plane, large_inds, large_probs, large_bins);
+}
+
+int gpdla_population_split_levels_cut_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
+                                          const double* offset_samples, const double* log_nhi_samples,
+                                          const double* min_z, const double* max_z, const int32_t* base_inds,
+                                          int32_t levels, const double* level_posteriors,
+                                          const gpdla_population_spec* spec, const gpdla_sample_cuts* cuts,
+                                          double* poisson_plane, int32_t* large_inds, double* large_probs,
+                                          int32_t* large_bins) {
+  return level_split_host(device, ll, rows, S, ld, offset_samples, log_nhi_samples, min_z, max_z, base_inds, levels,
+                          level_posteriors, spec, cuts, poisson_plane, large_inds, large_probs, large_bins);
 }
 
 }  // extern "C"

@@ -170,10 +170,44 @@ __device__ __forceinline__ int find_bin(const double* e, int n, double x) {
   return lo;
 }
 
+// ---- the search cuts of one row: uniform over the launch, and over the workgroup.  The
+// bitmap is read from global memory (a row's stretch is a few hundred bytes; the launches are no slower
+// with the cuts on than off, profiles/search_cuts/bench_c2.json and DESIGN.md section 22): the LDS
+// carves above are those of a launch without cuts
+struct RowCut {
+  bool prox, pix;
+  double z_upper;
+  int32_t n;
+  const uint32_t* words;
+};
+__device__ __forceinline__ RowCut row_cut(const SampleRowsArgs& r, int row) {
+  RowCut c{r.cut_z_upper != nullptr, r.cut_npix != nullptr, 0.0, 0, nullptr};
+  if (c.prox) c.z_upper = r.cut_z_upper[row];
+  if (c.pix) { c.n = r.cut_npix[row]; c.words = r.cut_words + r.cut_word_off[row]; }
+  return c;
+}
+// whether a slot at redshift z passes the cuts: z < z_upper, and pixel (int)(((z - min_z) / span) n) good, the
+// index formed in this operation order and truncated; an index outside [0, n), a NaN, n = 0 or span = 0 excludes
+__device__ __forceinline__ bool slot_kept(const RowCut& c, double zmin, double zmax, double z) {
+#pragma clang fp contract(off)
+  if (c.prox && !(z < c.z_upper)) return false;
+  if (c.pix) {
+    const double span = zmax - zmin;
+    const double t = (z - zmin) / span;
+    const double f = t * (double)c.n;
+    if (span == 0.0 || !(f > -1.0 && f < (double)c.n)) return false;
+    const int32_t i = (int32_t)f;
+    if (!((c.words[i >> 5] >> (i & 31)) & 1u)) return false;
+  }
+  return true;
+}
+
 // flat bin iz nn + in of sample ci on the grid staged at s_ez / s_en, or -1
-__device__ __forceinline__ int32_t sample_bin(const SampleRowsArgs& r, const double* s_ez, const double* s_en,
-                                              double zmin, double zmax, int32_t ci) {
-  const int iz = find_bin(s_ez, r.nz, sample_z(zmin, zmax, r.offset[ci]));
+__device__ __forceinline__ int32_t sample_bin(const SampleRowsArgs& r, const RowCut& cut, const double* s_ez,
+                                              const double* s_en, double zmin, double zmax, int32_t ci) {
+  const double z = sample_z(zmin, zmax, r.offset[ci]);
+  if ((cut.prox || cut.pix) && !slot_kept(cut, zmin, zmax, z)) return -1;
+  const int iz = find_bin(s_ez, r.nz, z);
   const int in = find_bin(s_en, r.nn, r.log_nhi[ci]);
   return (iz >= 0 && in >= 0) ? iz * r.nn + in : -1;
 }
@@ -219,6 +253,7 @@ __device__ __forceinline__ void planes_rows(const SampleRowsArgs& r, const doubl
   const int nb = r.nz * r.nn;
   stage_grid(r, tid, s_ez, s_en, s_pl, kSummaryPlanes * nb);
   const double zmin = r.zmin[row], zmax = r.zmax[row];
+  const RowCut cut = row_cut(r, row);
   for (uint32_t t0 = 0; t0 < S; t0 += kTile) {   // S <= INT32_MAX: 32 bits hold t0 + kTile
     __syncthreads();   // edges and zeroed planes ready; the previous tile's scan is over
     for (int i = tid; i < kTile; i += kRowThreads) {
@@ -235,7 +270,7 @@ __device__ __forceinline__ void planes_rows(const SampleRowsArgs& r, const doubl
 #pragma unroll
           for (int u = 0; u < NS; ++u) {
             nh[u] = nhi[c[u]];
-            b[u] = sample_bin(r, s_ez, s_en, zmin, zmax, c[u]);
+            b[u] = sample_bin(r, cut, s_ez, s_en, zmin, zmax, c[u]);
           }
         }
       }
@@ -330,6 +365,7 @@ __device__ __forceinline__ void split_rows(const SplitArgs& a, int row, int64_t 
   stage_grid(r, tid, s_ez, s_en, s_pl, nb);
   if (tid == 0) *cand.count = 0;
   const double zmin = r.zmin[row], zmax = r.zmax[row];
+  const RowCut cut = row_cut(r, row);
   for (uint32_t t0 = 0; t0 < S; t0 += kTile) {   // S <= INT32_MAX: 32 bits hold t0 + kTile
     __syncthreads();   // edges, zeroed plane and counter ready; the previous tile's scan is over
     for (int i = tid; i < kTile; i += kRowThreads) {
@@ -348,7 +384,7 @@ __device__ __forceinline__ void split_rows(const SplitArgs& a, int row, int64_t 
         if (p > a.p_thresh_sample && walk_chain<NS>(r, row, (int32_t)j, NS, c)) {
 #pragma unroll
           for (int u = 0; u < NS; ++u) {
-            b[u] = sample_bin(r, s_ez, s_en, zmin, zmax, c[u]);
+            b[u] = sample_bin(r, cut, s_ez, s_en, zmin, zmax, c[u]);
             any = any || b[u] >= 0;
           }
         }

@@ -245,7 +245,7 @@ class Engine:
 
     def _run_multi(self, packed, max_dlas, resample_uniforms, base_sample_inds, want_samples, min_z_separation,
                    occam_log_penalty, raise_numeric, memory, summary, sub=None, models=False, population=None,
-                   levels=None, intervals=None) -> dict:
+                   levels=None, intervals=None, cuts=None) -> dict:
         """process_multi / process_summaries / process_models / process_population: ``summary`` is None or
         the samples' log N_HI and the grid; ``sub`` None or the sub-DLA column densities (``nhi``) and, for the
         MAP outputs, their log10 (``log_nhi``); ``models`` routes the call through gpdla_engine_process_models,
@@ -253,7 +253,8 @@ class Engine:
         NULL) or the normalised dict of ``process_population``; ``levels`` (with ``models="population"``) routes
         it through gpdla_engine_process_levels with the halves it names ("planes", "split"); ``intervals`` (with
         ``summary`` alone) routes it through gpdla_engine_process_intervals: the samples' log N_HI, ``levels`` and
-        ``lr_delta``."""
+        ``lr_delta``; ``cuts`` (with ``models="population"``) routes it through gpdla_engine_process_cuts: the
+        normalised dict of ``process_cuts``."""
         D, S = int(max_dlas), self.num_samples
         offsets = np.ascontiguousarray(packed["offsets"], dtype=np.int64)
         Q = offsets.size - 1
@@ -370,6 +371,34 @@ class Engine:
                              population_level_large_probs=np.full((Q, Dc, NL), np.nan),
                              population_level_large_bins=np.full((Q, Dc, NL, L.MAX_DLAS), -1, dtype=np.int32))
 
+        cspec, cout = None, {}
+        if cuts is not None:
+            if intervals is not None or sub is not None:
+                raise ValueError("cuts do not cover the interval outputs or the sub-DLA model")
+            ces = summary["z_edges"] if summary is not None else None
+            cep = population["z_edges"] if population is not None else None
+            if ces is None and cep is None:
+                raise ValueError("cuts need a summary grid or population")
+            cspec = L.SearchCuts(proximity_zone=cuts["proximity_zone"], noise_thresh=cuts["noise_thresh"],
+                                 omega_m=cuts["omega_m"], num_z_bins_summary=0 if ces is None else ces.size - 1,
+                                 z_edges_summary=L.ptr(ces), num_z_bins_population=0 if cep is None else cep.size - 1,
+                                 z_edges_population=L.ptr(cep))
+            cout = dict(cut_z_uppers=np.full(Q, np.nan), cut_pixel_counts=np.zeros(Q, dtype=np.int32),
+                        cut_bitmap_offsets=np.zeros(Q + 1, dtype=np.int64),
+                        cut_bitmap_words=np.zeros(max(int(((np.diff(offsets) + 31) // 32).sum()), 1), dtype=np.uint32))
+            if ces is not None:
+                cout["cut_path_summary"] = np.zeros((Q, ces.size))
+            if cep is not None:
+                cout["cut_path_population"] = np.zeros((Q, cep.size))
+
+        def results_cuts(mem, get):
+            if cspec is None:
+                return None
+            return L.SearchCutResults(memory=mem, z_uppers=get("cut_z_uppers"), pixel_counts=get("cut_pixel_counts", C.c_int32),
+                                      bitmap_offsets=get("cut_bitmap_offsets", C.c_int64),
+                                      bitmap_words=get("cut_bitmap_words", C.c_uint32), path_summary=get("cut_path_summary"),
+                                      path_population=get("cut_path_population"))
+
         def results_levels(mem, get):
             if not lvout:
                 return None
@@ -397,7 +426,14 @@ class Engine:
                                 map_log_likelihoods=get("map_log_likelihood_lls"), map_z_lls=get("MAP_z_lls"),
                                 map_log_nhi_lls=get("MAP_log_nhi_lls"))
 
-        def call(sp, rs, sm, rsub=None, rpop=None, rlv=None, riv=None):
+        def call(sp, rs, sm, rsub=None, rpop=None, rlv=None, riv=None, rcut=None):
+            if cspec is not None:
+                return self.lib.gpdla_engine_process_cuts(
+                    self._h, C.byref(sp), C.byref(md), C.byref(subs) if subs is not None else None, C.byref(rs),
+                    C.byref(rsub) if rsub is not None else None, C.byref(spec) if spec is not None else None,
+                    C.byref(sm) if sm is not None else None, C.byref(pspec) if pspec is not None else None,
+                    C.byref(rpop) if rpop is not None else None, C.byref(rlv) if rlv is not None else None,
+                    C.byref(cspec), C.byref(rcut))
             if ispec is not None:
                 return self.lib.gpdla_engine_process_intervals(self._h, C.byref(sp), C.byref(md), C.byref(rs),
                                                                C.byref(spec), C.byref(sm), C.byref(ispec), C.byref(riv))
@@ -444,7 +480,8 @@ class Engine:
                       results_pop(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(pout[k], t) if pout[k].size else None),
                       results_levels(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(lvout[k], t) if k in lvout and lvout[k].size else None),
                       results_intervals(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(iout[k], t) if iout[k].size else None)
-                      if ispec is not None else None)
+                      if ispec is not None else None,
+                      results_cuts(L.MEM_HOST, lambda k, t=C.c_double: L.ptr(cout[k], t) if k in cout and cout[k].size else None))
         elif memory == "device":
             dev = {k: L.DeviceArray.from_numpy(v, self.device) for k, v in
                    dict(wl=wl, fl=fl, nv=nv, mk=mk, zq=zq).items()}
@@ -476,16 +513,20 @@ class Engine:
             dpop = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in pout.items() if v.size}
             dlv = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in lvout.items() if v.size}
             div = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in iout.items() if v.size}
+            dcut = {k: L.DeviceArray(self.device, v.shape, v.dtype) for k, v in cout.items()}   # (empty arrays too: non-null)
             rc = call(sp, rs, sm, results_sub(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dsub[k].ptr, t) if k in dsub else None),
                       results_pop(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dpop[k].ptr, t) if k in dpop else None),
                       results_levels(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dlv[k].ptr, t) if k in dlv else None),
                       results_intervals(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(div[k].ptr, t) if k in div else None)
-                      if ispec is not None else None)
+                      if ispec is not None else None,
+                      results_cuts(L.MEM_DEVICE, lambda k, t=C.c_double: L.dev_ptr(dcut[k].ptr, t) if k in dcut else None))
             if rc in (L.GPDLA_OK, L.GPDLA_ENUMERIC):
                 for k, d in dlv.items():
                     lvout[k] = d.numpy()
                 for k, d in div.items():
                     iout[k] = d.numpy()
+                for k, d in dcut.items():
+                    cout[k] = d.numpy()
                 for k, d in dpop.items():
                     pout[k] = d.numpy()
                 for k, d in dout.items():
@@ -494,7 +535,7 @@ class Engine:
                     sout[k] = d.numpy()
                 for k, d in dsub.items():
                     subout[k] = d.numpy()
-            for d in list(dev.values()) + list(dout.values()) + list(dsum.values()) + list(dsub.values()) + list(dpop.values()) + list(dlv.values()) + list(div.values()):
+            for d in list(dev.values()) + list(dout.values()) + list(dsum.values()) + list(dsub.values()) + list(dpop.values()) + list(dlv.values()) + list(div.values()) + list(dcut.values()):
                 d.free()
         else:
             raise ValueError("memory must be 'host' or 'device'")
@@ -511,6 +552,9 @@ class Engine:
         out.update(subout)
         out.update(pout)
         out.update(lvout)
+        if cspec is not None:
+            cout["cut_bitmap_words"] = cout["cut_bitmap_words"][:int(cout["cut_bitmap_offsets"][-1])]
+            out.update(cout, cut_proximity_zone=float(cuts["proximity_zone"]), cut_noise_thresh=float(cuts["noise_thresh"]))
         if ispec is not None:
             for key, v in iout.items():   # the C arrays are GPDLA_MAX_DLAS slots wide
                 out[key] = v if key == "lr_counts" else np.ascontiguousarray(v[:, :, :Dc])
@@ -559,7 +603,7 @@ class Engine:
                                     want_samples, True, None, kwargs)
 
     def _process_models(self, packed, max_dlas, sub_dla, log_nhi_samples, z_edges, log_nhi_edges, sub_dla_log_nhi,
-                        want_samples, entry, population, kwargs, levels=None) -> dict:
+                        want_samples, entry, population, kwargs, levels=None, cuts=None) -> dict:
         """``process_models`` / ``process_population`` / ``process_levels``: ``entry``, ``population`` and
         ``levels`` are ``_run_multi``'s ``models``, ``population`` and ``levels``."""
         if (z_edges is None) != (log_nhi_edges is None):
@@ -593,7 +637,7 @@ class Engine:
         return self._run_multi(packed, max_dlas, kwargs.get("resample_uniforms"), kwargs.get("base_sample_inds"),
                                want_samples, kwargs.get("min_z_separation"), kwargs.get("occam_log_penalty"),
                                kwargs.get("raise_numeric", False), kwargs.get("memory", "host"), summary, sub, entry,
-                               population, levels)
+                               population, levels, cuts=cuts)
 
     def process_population(self, packed: dict, max_dlas: int = 1, population=None, sub_dla=None, log_nhi_samples=None,
                            z_edges=None, log_nhi_edges=None, sub_dla_log_nhi=None, want_samples: bool = True,
@@ -670,6 +714,32 @@ class Engine:
         return self._process_models(packed, max_dlas, sub_dla, log_nhi_samples, z_edges, log_nhi_edges, sub_dla_log_nhi,
                                     want_samples, "population", self._population_dict(population), kwargs,
                                     levels=halves)
+
+    def process_cuts(self, packed: dict, max_dlas: int = 1, cuts=None, population=None, log_nhi_samples=None,
+                     z_edges=None, log_nhi_edges=None, want_samples: bool = True, levels=(), **kwargs) -> dict:
+        """``process_levels`` (its arguments pass through, without the sub-DLA model; ``levels=()`` by default, i.e.
+        ``process_population``) under the search cuts (gpdla_engine_process_cuts).  ``cuts``
+        is a dict of ``proximity_zone`` and ``noise_thresh`` (either None for off, not both) and optionally
+        ``omega_m`` (0.279).  Every grid reduction of the call -- ``bin_planes``, ``population_*``,
+        ``bin_planes_levels``, ``population_level_*`` -- drops the absorber slots in the proximity zone or on a
+        noisy pixel; every other array is unchanged bit for bit.  Adds ``cut_proximity_zone`` / ``cut_noise_thresh``
+        (NaN = off), ``cut_z_uppers`` (Q), ``cut_pixel_counts`` (Q), the good-pixel bitmap ``cut_bitmap_offsets``
+        (Q + 1) / ``cut_bitmap_words``, and the path columns ``cut_path_summary`` (Q x (nz + 1), with a summary
+        grid) and ``cut_path_population`` (with ``population``): each z bin, then the grid's whole extent.
+        ``cuts=None`` is ``process_levels``, bit for bit."""
+        have = (("planes",) if z_edges is not None else ()) + (("split",) if population is not None else ())
+        halves = have if levels is None else tuple(levels)
+        if set(halves) - {"planes", "split"}:
+            raise ValueError("levels names 'planes' and / or 'split'")
+        return self._process_models(packed, max_dlas, None, log_nhi_samples, z_edges, log_nhi_edges, None, want_samples,
+                                    "population", self._population_dict(population), kwargs, levels=halves,
+                                    cuts=normalise_cuts(cuts))
+
+    def cut_stats(self) -> dict:
+        """gpdla_engine_get_cut_stats: cumulative ms and count of the search-cut launches."""
+        ms, n = C.c_double(0.0), C.c_int64(0)
+        L.check(self.lib.gpdla_engine_get_cut_stats(self._h, C.byref(ms), C.byref(n)))
+        return dict(cut_ms=ms.value, cut_launches=n.value)
 
     def level_population_stats(self) -> dict:
         """gpdla_engine_get_level_population_stats: cumulative ms and count of the level-population launches."""
@@ -945,11 +1015,100 @@ def _level_rows(log_likelihoods, offset_samples, log_nhi_samples, min_z, max_z, 
     return ll, off, lognhi, zmin, zmax, base
 
 
+def normalise_cuts(cuts):
+    """``cuts`` of ``Engine.process_cuts`` / ``process_qsos`` as floats with NaN for off (None stays None).
+    ValueError for anything but a dict of ``proximity_zone``, ``noise_thresh`` (and ``omega_m``), for both off, and
+    for a negative or non-finite proximity zone."""
+    if cuts is None:
+        return None
+    known = {"proximity_zone", "noise_thresh", "omega_m"}
+    if not isinstance(cuts, dict) or set(cuts) - known:
+        raise ValueError(f"cuts must be a dict of {sorted(known)}")
+    pz, nt = cuts.get("proximity_zone"), cuts.get("noise_thresh")
+    pz = np.nan if pz is None else float(pz)
+    nt = np.nan if nt is None else float(nt)
+    if np.isnan(pz) and np.isnan(nt):
+        raise ValueError("cuts with both proximity_zone and noise_thresh off")
+    if not np.isnan(pz) and not (0.0 <= pz < np.inf):
+        raise ValueError("proximity_zone must be finite and >= 0")
+    om = float(cuts.get("omega_m", 0.279))
+    if not 0.0 < om <= 1.0:
+        raise ValueError("omega_m must lie in (0, 1]")
+    return dict(proximity_zone=pz, noise_thresh=nt, omega_m=om)
+
+
+def search_cuts(wavelengths, noise_variance, min_z, max_z, proximity_zone=None, noise_thresh=None,
+                z_edges_summary=None, z_edges_population=None, omega_m: float = 0.279, device: int = 0) -> dict:
+    """gpdla_search_cuts_f64: the proximity-zone and noisy-pixel cuts of every spectrum (include/gpdla.h "Search
+    cuts").  The two cell lists hold one vector per spectrum (taken as float64); ``None`` turns a cut off.
+    Returns ``cut_proximity_zone`` / ``cut_noise_thresh`` (NaN = off), ``cut_z_uppers`` [Q], ``cut_pixel_counts``
+    [Q], the good-pixel bitmap ``cut_bitmap_offsets`` [Q + 1] / ``cut_bitmap_words`` (uint32), and per grid
+    given ``cut_path_summary`` / ``cut_path_population`` [Q x (nz + 1)]: the path of each z bin, then of the
+    grid's whole extent.  The dict is what ``level_planes`` / ``population_split_levels`` take as ``cuts``."""
+    cells = [list(wavelengths), list(noise_variance)]
+    Q = len(cells[0])
+    if len(cells[1]) != Q:
+        raise ValueError("one cell per spectrum in each list")
+    offsets = np.zeros(Q + 1, dtype=np.int64)
+    np.cumsum([np.size(c) for c in cells[0]], out=offsets[1:])
+    flat = []
+    for lst in cells:
+        if any(np.size(c) != offsets[q + 1] - offsets[q] for q, c in enumerate(lst)):
+            raise ValueError("a spectrum's two vectors differ in length")
+        flat.append(np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.float64).ravel() for c in lst])
+                                         if Q else np.zeros(0)))
+    zmin = np.ascontiguousarray(min_z, dtype=np.float64).ravel()
+    zmax = np.ascontiguousarray(max_z, dtype=np.float64).ravel()
+    if zmin.size != Q or zmax.size != Q:
+        raise ValueError("one min_z and max_z per spectrum")
+    pz = np.nan if proximity_zone is None else float(proximity_zone)
+    nt = np.nan if noise_thresh is None else float(noise_thresh)
+    edges = [None if e is None else np.ascontiguousarray(e, dtype=np.float64).ravel()
+             for e in (z_edges_summary, z_edges_population)]
+    nzs = [0 if e is None else e.size - 1 for e in edges]
+    paths = [None if e is None else np.zeros((Q, max(nz, 0) + 1)) for e, nz in zip(edges, nzs)]
+    spec = L.SearchCuts(proximity_zone=pz, noise_thresh=nt, omega_m=float(omega_m), num_z_bins_summary=nzs[0],
+                        z_edges_summary=L.ptr(edges[0]), num_z_bins_population=nzs[1],
+                        z_edges_population=L.ptr(edges[1]))
+    z_uppers = np.zeros(Q)
+    counts = np.zeros(Q, dtype=np.int32)
+    woff = np.zeros(Q + 1, dtype=np.int64)
+    words = np.zeros(int(((np.diff(offsets) + 31) // 32).sum()) if Q else 0, dtype=np.uint32)
+    res = L.SearchCutResults(memory=L.MEM_HOST, z_uppers=L.ptr(z_uppers), pixel_counts=L.ptr(counts, C.c_int32),
+                             bitmap_offsets=L.ptr(woff, C.c_int64), bitmap_words=L.ptr(words, C.c_uint32),
+                             path_summary=L.ptr(paths[0]), path_population=L.ptr(paths[1]))
+    L.check(L.load().gpdla_search_cuts_f64(device, Q, L.ptr(offsets, C.c_int64), L.ptr(flat[0]), L.ptr(flat[1]), L.ptr(zmin),
+                                           L.ptr(zmax), C.byref(spec), C.byref(res)))
+    out = dict(cut_proximity_zone=pz, cut_noise_thresh=nt, cut_z_uppers=z_uppers, cut_pixel_counts=counts,
+               cut_bitmap_offsets=woff, cut_bitmap_words=words)
+    if paths[0] is not None:
+        out["cut_path_summary"] = paths[0]
+    if paths[1] is not None:
+        out["cut_path_population"] = paths[1]
+    return out
+
+
+def _sample_cuts(cuts, rows: int):
+    """gpdla_sample_cuts from ``search_cuts``'s dict, and the arrays it points to."""
+    prox = not np.isnan(cuts["cut_proximity_zone"])
+    pix = not np.isnan(cuts["cut_noise_thresh"])
+    zu = np.ascontiguousarray(cuts["cut_z_uppers"], dtype=np.float64).ravel() if prox else None
+    cnt = np.ascontiguousarray(cuts["cut_pixel_counts"], dtype=np.int32).ravel() if pix else None
+    woff = np.ascontiguousarray(cuts["cut_bitmap_offsets"], dtype=np.int64).ravel() if pix else None
+    words = np.ascontiguousarray(cuts["cut_bitmap_words"], dtype=np.uint32).ravel() if pix else None
+    if (zu is not None and zu.size != rows) or (cnt is not None and (cnt.size != rows or woff.size != rows + 1)):
+        raise ValueError("cuts must hold one entry per row")
+    spec = L.SampleCuts(z_uppers=L.ptr(zu), pixel_counts=L.ptr(cnt, C.c_int32), bitmap_offsets=L.ptr(woff, C.c_int64),
+                        bitmap_words=L.ptr(words, C.c_uint32))
+    return spec, (zu, cnt, woff, words)
+
+
 def level_planes(log_likelihoods, offset_samples, log_nhi_samples, nhi_samples, min_z, max_z, z_edges, log_nhi_edges,
-                 base_sample_inds=None, device: int = 0) -> np.ndarray:
+                 base_sample_inds=None, device: int = 0, cuts=None) -> np.ndarray:
     """The level-planes kernel alone (gpdla_level_planes_f64) on host arrays, with ``posterior_summary``'s
     inputs: ``log_likelihoods`` levels x rows x S, ``base_sample_inds`` (levels - 1) x rows x S (0-based, -1 =
-    none).  Returns ``bin_planes_levels``, rows x levels x 5 x nz x nn."""
+    none).  Returns ``bin_planes_levels``, rows x levels x 5 x nz x nn.  ``cuts`` (``search_cuts``'s dict, one
+    entry per row) applies the sample tests of the search cuts (gpdla_level_planes_cut_f64)."""
     ll, off, lognhi, zmin, zmax, base = _level_rows(log_likelihoods, offset_samples, log_nhi_samples, min_z, max_z,
                                                     base_sample_inds)
     levels, rows, S = ll.shape
@@ -962,19 +1121,27 @@ def level_planes(log_likelihoods, offset_samples, log_nhi_samples, nhi_samples, 
     spec = L.SummarySpec(log_nhi_samples=L.ptr(lognhi), num_z_bins=nz, num_nhi_bins=nn, z_edges=L.ptr(ez),
                          log_nhi_edges=L.ptr(en))
     planes = np.zeros((rows, levels, L.SUMMARY_PLANES, max(nz, 1), max(nn, 1)))
-    L.check(L.load().gpdla_level_planes_f64(
-        device, L.ptr(ll), rows, S, S, L.ptr(off), L.ptr(lognhi), L.ptr(nhi), L.ptr(zmin), L.ptr(zmax),
-        L.ptr(base, C.c_int32) if base is not None and base.size else None, levels, C.byref(spec), L.ptr(planes)))
+    bp = L.ptr(base, C.c_int32) if base is not None and base.size else None
+    if cuts is None:
+        L.check(L.load().gpdla_level_planes_f64(
+            device, L.ptr(ll), rows, S, S, L.ptr(off), L.ptr(lognhi), L.ptr(nhi), L.ptr(zmin), L.ptr(zmax), bp, levels,
+            C.byref(spec), L.ptr(planes)))
+    else:
+        cspec, _hold = _sample_cuts(cuts, rows)
+        L.check(L.load().gpdla_level_planes_cut_f64(
+            device, L.ptr(ll), rows, S, S, L.ptr(off), L.ptr(lognhi), L.ptr(nhi), L.ptr(zmin), L.ptr(zmax), bp, levels,
+            C.byref(spec), C.byref(cspec), L.ptr(planes)))
     return planes
 
 
 def population_split_levels(log_likelihoods, offset_samples, log_nhi_samples, min_z, max_z, level_posteriors, z_edges,
                             log_nhi_edges, base_sample_inds=None, p_thresh_sample: float = 1e-4,
-                            p_switch: float = 0.25, device: int = 0) -> dict:
+                            p_switch: float = 0.25, device: int = 0, cuts=None) -> dict:
     """The level-split kernel alone (gpdla_population_split_levels_f64) on host arrays: ``log_likelihoods``
     levels x rows x S, ``base_sample_inds`` (levels - 1) x rows x S, ``level_posteriors`` levels x rows (an
     input).  Returns ``Engine.process_levels``'s ``population_level_poisson`` (rows x levels x nz x nn),
-    ``population_level_large_inds`` / ``_probs`` (rows x levels x 8) and ``_bins`` (rows x levels x 8 x 4)."""
+    ``population_level_large_inds`` / ``_probs`` (rows x levels x 8) and ``_bins`` (rows x levels x 8 x 4).
+    ``cuts`` as in ``level_planes`` (gpdla_population_split_levels_cut_f64)."""
     ll, off, lognhi, zmin, zmax, base = _level_rows(log_likelihoods, offset_samples, log_nhi_samples, min_z, max_z,
                                                     base_sample_inds)
     levels, rows, S = ll.shape
@@ -992,10 +1159,17 @@ def population_split_levels(log_likelihoods, offset_samples, log_nhi_samples, mi
     inds = np.full((rows, levels, NL), -1, dtype=np.int32)
     bins = np.full((rows, levels, NL, L.MAX_DLAS), -1, dtype=np.int32)
     probs = np.full((rows, levels, NL), np.nan)
-    L.check(L.load().gpdla_population_split_levels_f64(
-        device, L.ptr(ll), rows, S, S, L.ptr(off), L.ptr(lognhi), L.ptr(zmin), L.ptr(zmax),
-        L.ptr(base, C.c_int32) if base is not None and base.size else None, levels, L.ptr(P), C.byref(spec),
-        L.ptr(plane), L.ptr(inds, C.c_int32), L.ptr(probs), L.ptr(bins, C.c_int32)))
+    bp = L.ptr(base, C.c_int32) if base is not None and base.size else None
+    outs = (L.ptr(plane), L.ptr(inds, C.c_int32), L.ptr(probs), L.ptr(bins, C.c_int32))
+    if cuts is None:
+        L.check(L.load().gpdla_population_split_levels_f64(
+            device, L.ptr(ll), rows, S, S, L.ptr(off), L.ptr(lognhi), L.ptr(zmin), L.ptr(zmax), bp, levels, L.ptr(P),
+            C.byref(spec), *outs))
+    else:
+        cspec, _hold = _sample_cuts(cuts, rows)
+        L.check(L.load().gpdla_population_split_levels_cut_f64(
+            device, L.ptr(ll), rows, S, S, L.ptr(off), L.ptr(lognhi), L.ptr(zmin), L.ptr(zmax), bp, levels, L.ptr(P),
+            C.byref(spec), C.byref(cspec), *outs))
     return dict(population_level_poisson=plane, population_level_large_inds=inds, population_level_large_probs=probs,
                 population_level_large_bins=bins)
 

@@ -341,12 +341,15 @@ def _interval_spec(intervals):
 
 
 def _compute_kwargs(max_dlas: int, summaries, save_samples: bool, sub=None, forest=None, population=None,
-                    intervals=None) -> dict:
+                    intervals=None, cuts=None) -> dict:
     """What a ``compute`` replacement is told beyond the five positional arguments: only what differs
     from the plain single-DLA call, so existing replacements keep working.  ``sub_dla`` is the normalised
     dict(nhi, log_nhi, ratio), ``forest`` the full settings dict, ``population`` the normalised dict of
-    ``_population_spec`` with the log priors of ``_model_log_priors`` added."""
+    ``_population_spec`` with the log priors of ``_model_log_priors`` added, ``cuts`` the dict of
+    ``engine.normalise_cuts`` (NaN = off)."""
     kw = {}
+    if cuts is not None:
+        kw["cuts"] = cuts
     if population is not None:
         kw["population"] = population
     if sub is not None:
@@ -366,7 +369,8 @@ def _compute_kwargs(max_dlas: int, summaries, save_samples: bool, sub=None, fore
 
 def _engine_compute(model: dict, samples: dict, packed: dict, params: Parameters, device: int = 0,
                     engine: Engine | None = None, max_dlas: int = 1, summaries=None, save_samples: bool = True,
-                    timings: dict | None = None, sub_dla=None, forest=None, population=None, intervals=None) -> dict:
+                    timings: dict | None = None, sub_dla=None, forest=None, population=None, intervals=None,
+                    cuts=None) -> dict:
     """The hot path on the GPU: per-spectrum null / sample / DLA log likelihoods and z ranges; with
     ``max_dlas`` > 1 every level of the multi-DLA search (Engine.process_multi's arrays); with
     ``summaries`` the posterior summaries as well (Engine.process_summaries), the sample arrays only if
@@ -374,7 +378,9 @@ def _engine_compute(model: dict, samples: dict, packed: dict, params: Parameters
     (Engine.process_models); ``forest`` (the settings dict) is set on the engine for this call and cleared
     after it.  ``population`` (the dict ``_compute_kwargs`` documents) adds Engine.process_population's arrays;
     ``levels="all"`` in either dict routes the call through Engine.process_levels for that half.  ``intervals``
-    (the dict of ``_interval_spec``; with ``summaries`` alone) adds Engine.process_intervals's arrays."""
+    (the dict of ``_interval_spec``; with ``summaries`` alone) adds Engine.process_intervals's arrays.  ``cuts``
+    (the dict of ``engine.normalise_cuts``) routes the call through Engine.process_cuts: the grid reductions
+    under the search cuts, and the cut variables."""
     grid = _summary_grid(summaries)
     halves = (("planes",) if _summary_levels(summaries) else ()) + \
              (("split",) if population is not None and population.get("levels") == "all" else ())
@@ -382,6 +388,25 @@ def _engine_compute(model: dict, samples: dict, packed: dict, params: Parameters
     try:
         if forest is not None:
             eng.set_forest(forest)
+        if cuts is not None:
+            if "log_nhi_samples" not in samples:
+                raise ValueError("cuts need samples['log_nhi_samples']")
+            popd = None
+            if population is not None:
+                popd = {k: v for k, v in population.items() if k != "levels"}
+                popd["log_nhi_samples"] = samples["log_nhi_samples"]
+            res = eng.process_cuts(
+                packed, max_dlas, cuts={k: (None if np.isnan(v) else v) for k, v in cuts.items()}, population=popd,
+                log_nhi_samples=samples["log_nhi_samples"] if grid is not None else None,
+                z_edges=grid[0] if grid is not None else None, log_nhi_edges=grid[1] if grid is not None else None,
+                want_samples=save_samples, levels=halves)
+            if max_dlas == 1:   # Engine.process's shapes: no level axis, no multi-DLA variables
+                res["log_likelihoods_dla"] = res["log_likelihoods_dla"][0]
+                if "sample_log_likelihoods_dla" in res:
+                    res["sample_log_likelihoods_dla"] = res["sample_log_likelihoods_dla"][0]
+                res.pop("base_sample_inds", None)
+                res.pop("max_dlas", None)
+            return res
         if halves:
             if "log_nhi_samples" not in samples:
                 raise ValueError("levels='all' needs samples['log_nhi_samples']")
@@ -599,6 +624,26 @@ def _finish_population(out: dict, res: dict, pop: dict) -> dict:
     return out
 
 
+def _finish_cuts(out: dict, res: dict, cuts: dict, summaries, pop: dict | None) -> dict:
+    """Add CUT_VARIABLES to the saved ones.  ``res`` holds Engine.process_cuts's arrays; a threshold that is off
+    is saved as NaN, and a path array only with its grid."""
+    Q = np.asarray(out["log_likelihoods_no_dla"]).size
+    out["cut_proximity_zone"], out["cut_noise_thresh"] = float(cuts["proximity_zone"]), float(cuts["noise_thresh"])
+    out["cut_omega_m"] = float(cuts["omega_m"])
+    out["cut_z_uppers"] = np.asarray(res["cut_z_uppers"], dtype=np.float64).reshape(Q)
+    out["cut_pixel_counts"] = np.asarray(res["cut_pixel_counts"], dtype=np.float64).reshape(Q)
+    grid = _summary_grid(summaries)
+    for key, edges in (("cut_path_summary", None if grid is None else grid[0]),
+                       ("cut_path_population", None if pop is None else pop["z_edges"])):
+        if edges is None:
+            continue
+        v = np.asarray(res[key], dtype=np.float64)
+        if v.shape != (Q, np.size(edges)):
+            raise ValueError(f"{key} must be {(Q, np.size(edges))}")
+        out[key] = v
+    return out
+
+
 def _finish_levels(out: dict, res: dict, summaries, pop: dict | None, max_dlas: int) -> dict:
     """Add the LEVEL_POPULATION_VARIABLES a ``levels="all"`` run produced.  ``res`` holds Engine.process_levels's
     arrays; the level posteriors become Q x D, the sample indices and the flat bins 1-based doubles with
@@ -671,7 +716,7 @@ def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
                  params: Parameters | None = None, test_ind=None, engine: Engine | None = None,
                  device: int = 0, metadata: dict | None = None, max_dlas: int = 1, compute=None,
                  summaries=None, save_samples: bool = True, sub_dla=None, forest=None, population=None,
-                 intervals=None) -> dict:
+                 intervals=None, cuts=None) -> dict:
     """Run the DLA search (process_qsos.m:88-232) and return the saved variables.  ``max_dlas`` > 1
     (up to 4) runs the multi-DLA search: ``log_likelihoods_dla`` / ``log_priors_dla`` /
     ``log_posteriors_dla`` become Q x D, ``model_posteriors`` Q x (1 + D), ``sample_log_likelihoods_dla``
@@ -731,9 +776,30 @@ def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
     ``save_samples=False``.  With ``population``, ``sub_dla`` or ``levels="all"`` it raises ValueError: those
     calls do not carry the interval launches (the sub-DLA model has no intervals yet).  Without the keyword
     every variable is as before, bit for bit.  A ``compute`` replacement receives ``intervals=`` (dict(levels,
-    lr_delta)) when it is set."""
+    lr_delta)) when it is set.
+
+    ``cuts`` (``dict(proximity_zone=0.1, noise_thresh=0.25)``, either None for off; optionally ``omega_m``) applies
+    the reference's ``lowzcut`` and ``filter_noisy_pixels`` (Engine.process_cuts) inside every
+    grid reduction of the call -- ``bin_planes``, the POPULATION_VARIABLES and, with ``levels="all"``, the
+    LEVEL_POPULATION_VARIABLES -- and adds CUT_VARIABLES: the thresholds (NaN = off), ``cut_z_uppers`` and
+    ``cut_pixel_counts`` (Q) and the per-spectrum path columns ``cut_path_summary`` / ``cut_path_population``
+    (Q x (nz + 1): each z bin of the grid, then its whole extent), which catalog.py's population functions then use
+    in place of the uncut path.  It needs a summary grid or ``population`` (ValueError otherwise, and for both
+    thresholds None); with ``intervals`` or ``sub_dla`` it raises ValueError: the cuts do not cover the interval
+    outputs or the sub-DLA model.  Every variable that is not a grid reduction is as before, bit for bit, and so
+    is everything without the keyword.  A ``compute`` replacement receives ``cuts=`` (dict(proximity_zone,
+    noise_thresh, omega_m), NaN = off) and returns the ``cut_*`` arrays of Engine.process_cuts."""
     if not 1 <= int(max_dlas) <= 4:
         raise ValueError("max_dlas must be 1..4")
+    from .engine import normalise_cuts
+    cts = normalise_cuts(cuts)
+    if cts is not None:
+        if intervals is not None and intervals is not False:
+            raise ValueError("cuts do not combine with intervals: the interval outputs are not cut")
+        if sub_dla is not None and sub_dla is not False:
+            raise ValueError("cuts do not combine with sub_dla: the sub-DLA model is not cut")
+        if _summary_grid(summaries) is None and (population is None or population is False):
+            raise ValueError("cuts need a summary grid or population: there is no grid reduction to cut")
     ivs = _interval_spec(intervals)
     if ivs is not None:
         if population is not None and population is not False:
@@ -754,10 +820,10 @@ def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
         popkw = dict(pop, log_priors_no_dla=lp_no, log_priors_dla=lp_dla, log_priors_lls=lp_lls)
     if compute is not None:
         res = compute(model, samples, packed, params, device,
-                      **_compute_kwargs(max_dlas, summaries, save_samples, sub, fst, popkw, ivs))
+                      **_compute_kwargs(max_dlas, summaries, save_samples, sub, fst, popkw, ivs, cts))
     else:
         res = _engine_compute(model, samples, packed, params, device, engine, max_dlas, summaries, save_samples,
-                              sub_dla=sub, forest=fst, population=popkw, intervals=ivs)
+                              sub_dla=sub, forest=fst, population=popkw, intervals=ivs, cuts=cts)
     if not save_samples:
         res = {k: v for k, v in res.items() if k not in ("sample_log_likelihoods_dla", "base_sample_inds",
                                                          "sample_log_likelihoods_lls")}
@@ -767,6 +833,8 @@ def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
     if pop is not None:
         _finish_population(out, res, pop)
     _finish_levels(out, res, summaries, pop, max_dlas)
+    if cts is not None:
+        _finish_cuts(out, res, cts, summaries, pop)
     if test_ind is not None:
         out["test_ind"] = np.asarray(test_ind)
     return out
@@ -807,6 +875,10 @@ LEVEL_POPULATION_VARIABLES = ("bin_planes_levels", "population_level_posteriors"
 # what a run with the posterior intervals saves besides (process_qsos(intervals=...)); catalog.py reads them
 INTERVAL_VARIABLES = ("z_dla_quantiles", "log_nhi_quantiles", "interval_levels", "z_dla_means", "z_dla_sds",
                       "log_nhi_means", "log_nhi_sds", "z_dla_lr_ranges", "log_nhi_lr_ranges", "lr_counts", "lr_delta")
+# what a run under the search cuts saves besides (process_qsos(cuts=...)): the thresholds (NaN = off), the upper
+# ends and pixel counts, and the per-spectrum path columns catalog.py reads in place of the uncut path
+CUT_VARIABLES = ("cut_proximity_zone", "cut_noise_thresh", "cut_omega_m", "cut_z_uppers", "cut_pixel_counts",
+                 "cut_path_summary", "cut_path_population")
 
 
 def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
@@ -830,12 +902,13 @@ def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
     ``model_posteriors[2]`` still reads "exactly two DLAs", calc_cddf.py:67), one with ``forest`` the
     FOREST_VARIABLES (and, with a ``mean_flux_scope`` other than "mu", MEAN_FLUX_SCOPE_VARIABLES), one
     with ``population`` the POPULATION_VARIABLES, one with ``levels="all"`` the LEVEL_POPULATION_VARIABLES
-    (h5py sees ``bin_planes_levels`` as (nn, nz, 5, D, Q)), one with ``intervals`` the INTERVAL_VARIABLES."""
+    (h5py sees ``bin_planes_levels`` as (nn, nz, 5, D, Q)), one with ``intervals`` the INTERVAL_VARIABLES, one
+    with ``cuts`` the CUT_VARIABLES."""
     mat = {}
     multi = int(np.ravel(out.get("max_dlas", 1))[0]) > 1
     for key in (PROCESSED_VARIABLES + (MULTI_DLA_VARIABLES if multi else ()) + SUMMARY_VARIABLES + SUB_DLA_VARIABLES +
                 FOREST_VARIABLES + MEAN_FLUX_SCOPE_VARIABLES + POPULATION_VARIABLES + LEVEL_POPULATION_VARIABLES +
-                INTERVAL_VARIABLES):
+                INTERVAL_VARIABLES + CUT_VARIABLES):
         if key not in out:
             continue
         v = out[key]

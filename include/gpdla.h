@@ -772,6 +772,105 @@ int gpdla_spectrum_snrs_f64(int32_t device, int64_t Q, const int64_t* offsets, c
                             const double* flux, const double* noise_variance, const double* max_z_dlas,
                             const double* normalizers, double* snrs);
 
+/* ---- Search cuts: proximity zone and noisy pixels --------------------------------
+ * calc_cddf.py's `lowzcut` (:352, :739-741) and `filter_noisy_pixels` (:387-438, :746-747, :934) as one
+ * launch over CSR spectra: per spectrum q, with min_z / max_z its search range and span = max_z - min_z,
+ * every operation in double and rounded on its own (no FMA):
+ *   pixels      those with 1215.67 (1 + min_z) < wavelength < 1215.67 (1 + max_z) (both strict), in pixel
+ *               order, pixel_counts[q] = n of them; the pixel mask is not consulted.  Pixel i of them is good
+ *               when noise_variance < noise_thresh (NaN, +inf and equality are bad); with the pixel cut off
+ *               (noise_thresh NaN) every one is good.  bitmap_words holds the good flags, bit i of the
+ *               spectrum's stretch (word i / 32, bit i % 32), the stretch starting at word bitmap_offsets[q]
+ *               and ceil(len_q / 32) words long; the bits from n on are 0
+ *   z_uppers    max(max_z - proximity_zone, min_z), or max_z with the proximity cut off (proximity_zone NaN)
+ *   samples     the reductions given these results (gpdla_sample_cuts below) put an absorber slot at
+ *               redshift z into a bin only if z < z_upper (proximity cut on) and pixel
+ *               (int)(((z - min_z) / span) n) is good (pixel cut on; this operation order, truncated; an index
+ *               outside [0, n), a NaN, n = 0 or span = 0 excludes the slot).  Nothing else about a sample
+ *               changes: its mass still counts in W, a void chain still voids it, and a surviving slot of a
+ *               multi-DLA sample counts though a sibling is cut
+ *   path        per grid given, nz + 1 values per spectrum: bins [e_c, e_c+1], then the whole extent
+ *               [e_0, e_nz].  For [z_lo, z_hi]: 0 unless min_z < z_hi and z_upper > z_lo; pmin = max(z_lo,
+ *               min_z), pmax = min(z_hi, z_upper); X(pmax) - X(pmin) when every pixel is good (n >= 1) or the
+ *               pixel cut is off; 0 when n = 0, or n = 1 with its pixel bad; otherwise with zz_i = min_z +
+ *               (span i) / (n - 1) the sum over the starts -- pixels i < n - 1, good, pmin <= zz_i <= pmax, and
+ *               i = 0 or pixel i - 1 not (good with zz >= pmin) -- of X(zz_(e-1)) - X(zz_i) when e, the first
+ *               bad pixel after i, exists and zz_e < pmax, else X(pmax) - X(zz_i).  X(z) = 2 sqrt(omega_m
+ *               (1 + z)^3 + 1 - omega_m) / (3 omega_m), the cube as two products.  The terms are added as
+ *               strided per-thread partial sums in pixel order, a 64-lane xor butterfly and the waves in
+ *               order: fixed by n alone
+ * No floating-point atomics; a spectrum's outputs are a function of the spectrum alone, so repeated calls
+ * and any batching agree bit for bit. */
+typedef struct gpdla_search_cuts {
+  double proximity_zone;             /* finite and >= 0 (calc_cddf.py: 0.1), or NaN: off */
+  double noise_thresh;               /* NaN: off */
+  double omega_m;                    /* in (0, 1]; read only with a grid */
+  int32_t num_z_bins_summary;        /* 0: no summary grid */
+  const double* z_edges_summary;     /* host [nz + 1], finite, strictly increasing */
+  int32_t num_z_bins_population;     /* 0: no population grid */
+  const double* z_edges_population;
+} gpdla_search_cuts;
+
+typedef struct gpdla_search_cut_results {
+  int32_t memory;                    /* GPDLA_MEM_HOST; gpdla_engine_process_cuts also takes GPDLA_MEM_DEVICE */
+  double* z_uppers;                  /* [Q] */
+  int32_t* pixel_counts;             /* [Q] */
+  int64_t* bitmap_offsets;           /* [Q + 1], written: sum over the spectra before q of ceil(len / 32) */
+  uint32_t* bitmap_words;            /* [sum_q ceil(len_q / 32)] */
+  double* path_summary;              /* [Q][nz + 1], or NULL without the summary grid */
+  double* path_population;           /* [Q][nz_p + 1], or NULL without the population grid */
+} gpdla_search_cut_results;
+
+/* The kernel alone, host buffers: spectrum q's pixels are offsets[q] .. offsets[q + 1].  One span.
+ * GPDLA_EINVAL for Q < 1, offsets not ascending from 0, both thresholds NaN, a negative or infinite
+ * proximity_zone, a malformed grid, omega_m outside (0, 1] with a grid, a grid without its path array or a
+ * path array without its grid, a null array, or memory other than GPDLA_MEM_HOST. */
+int gpdla_search_cuts_f64(int32_t device, int64_t Q, const int64_t* offsets, const double* wavelengths,
+                          const double* noise_variance, const double* min_z, const double* max_z,
+                          const gpdla_search_cuts* cuts, const gpdla_search_cut_results* results);
+
+/* What the reductions read of a cut (host arrays): the outputs above, row r of the reduction being spectrum r. */
+typedef struct gpdla_sample_cuts {
+  const double* z_uppers;            /* [rows], or NULL: no proximity test */
+  const int32_t* pixel_counts;       /* [rows], or NULL: no pixel test */
+  const int64_t* bitmap_offsets;     /* [rows + 1] with pixel_counts: ascending from 0 */
+  const uint32_t* bitmap_words;      /* [bitmap_offsets[rows]] */
+} gpdla_sample_cuts;
+/* gpdla_level_planes_f64 and gpdla_population_split_levels_f64 with the two sample tests above applied to every
+ * absorber slot of every level (levels = 1: the level-1 rule).  cuts NULL: those calls, bit for bit.
+ * GPDLA_EINVAL additionally for cuts with neither test, pixel_counts without the bitmap, offsets not ascending
+ * from 0, or a pixel count outside [0, 32 words of the row]. */
+int gpdla_level_planes_cut_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
+                               const double* offset_samples, const double* log_nhi_samples, const double* nhi_samples,
+                               const double* min_z, const double* max_z, const int32_t* base_inds, int32_t levels,
+                               const gpdla_summary_spec* spec, const gpdla_sample_cuts* cuts, double* bin_planes);
+int gpdla_population_split_levels_cut_f64(int32_t device, const double* ll, int64_t rows, int64_t S, int64_t ld,
+                                          const double* offset_samples, const double* log_nhi_samples,
+                                          const double* min_z, const double* max_z, const int32_t* base_inds,
+                                          int32_t levels, const double* level_posteriors,
+                                          const gpdla_population_spec* spec, const gpdla_sample_cuts* cuts,
+                                          double* poisson_plane, int32_t* large_inds, double* large_probs,
+                                          int32_t* large_bins);
+
+/* gpdla_engine_process_levels plus the search cuts: with cuts and results both NULL it is that call, bit for
+ * bit; with them every output that is not a grid reduction (evidences, sample rows, MAP values, posteriors) is
+ * unchanged bit for bit, and every grid reduction of the call -- gpdla_summaries.bin_planes, gpdla_population
+ * and gpdla_level_population -- applies the sample tests.  The cut launch runs per device batch once min_z /
+ * max_z exist and before the first grid reduction, on the batch's resident pixels; the noise variance is the
+ * one the engine was given.  results may be host or device memory; the path grids are the cuts' own edge
+ * arrays.  GPDLA_EINVAL for one of the two NULL and the other not, the gpdla_search_cuts_f64 cases, or a call
+ * with neither a summary grid nor a population spec; GPDLA_EUNSUPPORTED with the sub-DLA model and on int8 and
+ * panel-GEMM engines. */
+int gpdla_engine_process_cuts(gpdla_engine* engine, const gpdla_spectra* spectra,
+                              const gpdla_multi_dla* multi, const gpdla_sub_dla* sub,
+                              const gpdla_results_multi* results_multi, const gpdla_results_sub* results_sub,
+                              const gpdla_summary_spec* spec, const gpdla_summaries* summaries,
+                              const gpdla_population_spec* pspec, const gpdla_population* population,
+                              const gpdla_level_population* levels, const gpdla_search_cuts* cuts,
+                              const gpdla_search_cut_results* results);
+/* Cumulative kernel time (HIP events) and count of the search-cut launches since create / reset_stats. */
+int gpdla_engine_get_cut_stats(gpdla_engine* engine, double* ms, int64_t* launches);
+
 /* ---- Count mixture: the total column of a redshift bin on a lattice -------------------
  * calc_cddf.py's _get_omega_confidence_intervals (:562-636) combines the count distributions of a redshift
  * bin's column-density bins into the distribution of T = sum_b n_b N_b.  Here T lives on a dense fp64 lattice of
