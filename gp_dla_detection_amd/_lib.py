@@ -79,6 +79,24 @@ class Stats(C.Structure):
 MAX_DLAS = 4
 
 
+class ModelAbsorbers(C.Structure):
+    _fields_ = [("counts", i32p), ("z_dlas", dp), ("log_nhis", dp), ("nhis", dp)]
+
+
+class ModelSpectra(C.Structure):
+    _fields_ = [("memory", C.c_int32), ("cap_offsets", i64p), ("pixel_inds", i32p), ("absorption", dp),
+                ("model_mean", dp), ("continuum_mean", dp), ("continuum_sd", dp), ("chi2", dp),
+                ("log_likelihoods", dp), ("num_pixels", i32p), ("levels", i32p)]
+
+
+MODEL_LEVEL_BEST = 0
+MODEL_LEVEL_GIVEN = 1
+
+
+class ModelLevels(C.Structure):
+    _fields_ = [("level_mode", C.c_int32), ("levels", i32p), ("log_priors_dla", dp)]
+
+
 class MultiDla(C.Structure):
     _fields_ = [("max_dlas", C.c_int32), ("min_z_separation", C.c_double), ("occam_log_penalty", C.c_double),
                 ("resample_uniforms", dp), ("forced_base_inds", i32p)]
@@ -279,6 +297,14 @@ SIGNATURES = {
     "gpdla_population_split_levels_cut_f64": (C.c_int, [C.c_int32, dp, C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, dp,
                                                         i32p, C.c_int32, dp, C.POINTER(PopulationSpec),
                                                         C.POINTER(SampleCuts), dp, i32p, dp, i32p]),
+    "gpdla_engine_model_spectra": (C.c_int, [C.c_void_p, C.POINTER(Spectra), C.POINTER(ModelAbsorbers),
+                                             C.POINTER(ModelSpectra)]),
+    "gpdla_engine_process_spectra_models": (C.c_int, [C.c_void_p, C.POINTER(Spectra), C.POINTER(MultiDla),
+                                                      C.POINTER(ResultsMulti), C.POINTER(SummarySpec),
+                                                      C.POINTER(Summaries), C.POINTER(IntervalSpec),
+                                                      C.POINTER(Intervals), C.POINTER(ModelLevels),
+                                                      C.POINTER(ModelSpectra)]),
+    "gpdla_engine_get_model_spectra_stats": (C.c_int, [C.c_void_p, dp, i64p]),
     "gpdla_count_mixture_f64": (C.c_int, [C.c_int32, dp, i32p, i64p, i64p, C.c_int64, C.c_int64, dp, C.c_int32, i32p, i32p,
                                           dp, dp]),
     "gpdla_count_mixture_tiling": (C.c_int, [i32p, i32p, i32p]),

@@ -8,7 +8,7 @@ from pathlib import Path
 
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
-SOURCES = ["kernels.hip", "kernels_i8.hip", "gemm_path.hip", "gemm_i8.hip", "gemm_f64.hip", "multi_dla.hip", "posterior_summary.hip", "posterior_intervals.hip", "population.hip", "level_population.hip", "bootstrap.hip", "snr.hip", "search_cuts.hip", "count_mixture.hip", "forest.hip", "engine.hip", "objective.hip",
+SOURCES = ["kernels.hip", "kernels_i8.hip", "gemm_path.hip", "gemm_i8.hip", "gemm_f64.hip", "multi_dla.hip", "posterior_summary.hip", "posterior_intervals.hip", "population.hip", "level_population.hip", "bootstrap.hip", "snr.hip", "search_cuts.hip", "count_mixture.hip", "forest.hip", "model_spectra.hip", "engine.hip", "objective.hip",
            "dla_samples.hip", "ingest.hip", "faddeeva_host.cpp"]
 OUT = PKG / "libgpdla.so"
 

@@ -906,3 +906,64 @@ def write_absorber_catalog(directory: str, test_set_name: str, catalog: dict, ou
                            _fmt(spec, t[prefix + "_lr_lo"][i]), _fmt(spec, t[prefix + "_lr_hi"][i])]
             f.write(" ".join(fields) + "\n")
     return path
+
+
+# ------------------------------------------------------------------------------------------ model spectra
+# what Engine.model_spectra returns, under the names an output dictionary carries them by
+MODEL_SPECTRA_KEYS = dict(offsets="model_offsets", pixel_inds="model_pixel_inds", absorption="model_absorption",
+                          model_mean="model_mean", continuum="model_continuum", continuum_sd="model_continuum_sd",
+                          log_likelihoods="model_log_likelihoods", chi2="model_chi2", num_pixels="model_num_pixels")
+
+
+def model_spectra_variables(result: dict) -> dict:
+    """``Engine.model_spectra``'s result under the ``model_*`` names the helpers below read."""
+    return {new: result[old] for old, new in MODEL_SPECTRA_KEYS.items()}
+
+
+def model_spectrum(out: dict, q: int, wavelengths=None) -> dict:
+    """Spectrum ``q``'s slices of the flat ``model_*`` arrays: ``pixel_inds`` (within the spectrum), ``absorption``,
+    ``model_mean``, ``continuum``, ``continuum_sd``, the posterior absorbed fit ``fit`` = absorption * continuum,
+    the scalars ``chi2``, ``log_likelihood``, ``num_pixels`` and, with the spectrum's own ``wavelengths``, those at
+    ``pixel_inds``."""
+    off = np.asarray(out["model_offsets"], dtype=np.int64)
+    if not 0 <= q < off.size - 1:
+        raise IndexError(f"spectrum {q} outside 0..{off.size - 2}")
+    sl = slice(int(off[q]), int(off[q + 1]))
+    r = dict(pixel_inds=np.asarray(out["model_pixel_inds"])[sl], absorption=np.asarray(out["model_absorption"])[sl],
+             model_mean=np.asarray(out["model_mean"])[sl], continuum=np.asarray(out["model_continuum"])[sl],
+             continuum_sd=np.asarray(out["model_continuum_sd"])[sl], chi2=float(np.asarray(out["model_chi2"])[q]),
+             log_likelihood=float(np.asarray(out["model_log_likelihoods"])[q]),
+             num_pixels=int(np.asarray(out["model_num_pixels"])[q]))
+    r["fit"] = r["absorption"] * r["continuum"]
+    if wavelengths is not None:
+        r["wavelengths"] = np.asarray(wavelengths, dtype=np.float64)[r["pixel_inds"]]
+    return r
+
+
+def dla_pixel_mask(out: dict, min_transmission: float = 0.8) -> np.ndarray:
+    """Flat bool array over the ``model_*`` pixels: True where the absorbers transmit less than
+    ``min_transmission`` (the cores a Lyman-alpha forest analysis masks).  NaN absorption is not masked."""
+    if not 0.0 <= min_transmission <= 1.0:
+        raise ValueError("min_transmission must lie in [0, 1]")
+    with np.errstate(invalid="ignore"):
+        return np.asarray(out["model_absorption"], dtype=np.float64) < min_transmission
+
+
+def wing_correction(out: dict, min_transmission: float = 0.8) -> np.ndarray:
+    """1 / absorption where ``dla_pixel_mask`` is False (the factor that divides the damping wings out of the
+    flux), NaN where it is True."""
+    a = np.asarray(out["model_absorption"], dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(dla_pixel_mask(out, min_transmission), np.nan, 1.0 / a)
+
+
+def fit_quality(out: dict) -> dict:
+    """Per spectrum ``reduced_chi2`` = chi2 / n and ``z_score`` = (chi2 - n) / sqrt(2 n): under the model chi2 =
+    r'K^-1 r is chi-squared with n degrees of freedom (mean n, variance 2 n), so z_score is its standardised
+    residual -- near 0 for a sightline the model describes, many units above it for one it cannot (a BAL, a bad
+    reduction).  NaN for a spectrum without pixels."""
+    chi2 = np.asarray(out["model_chi2"], dtype=np.float64)
+    n = np.asarray(out["model_num_pixels"], dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return dict(reduced_chi2=np.where(n > 0, chi2 / n, np.nan),
+                    z_score=np.where(n > 0, (chi2 - n) / np.sqrt(2 * n), np.nan))

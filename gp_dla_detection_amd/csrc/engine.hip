@@ -101,7 +101,8 @@ struct TimedLaunch {
              // 7 posterior summaries (gpdla_engine_process_summaries); 8 forest kernels; gpdla_engine_process_models
              // only: 9 sub-DLA sweep, 10 its log-mean-exp and MAP launches; 11 population launches
              // (gpdla_engine_process_population); 12 level-population launches (gpdla_engine_process_levels);
-             // 13 posterior intervals (gpdla_engine_process_intervals); 14 search cuts (gpdla_engine_process_cuts)
+             // 13 posterior intervals (gpdla_engine_process_intervals); 14 search cuts (gpdla_engine_process_cuts);
+             // 15 model spectra (gpdla_engine_model_spectra)
   int level; // multi-DLA level the span also counts for in gpdla_multi_stats (0: none)
 };
 
@@ -263,6 +264,14 @@ struct gpdla_engine {
   size_t cap_c_zu = 0, cap_c_path[2] = {0, 0}, cap_c_edges = 0, cap_c_np = 0, cap_c_wo = 0, cap_c_words = 0;
   double cut_ms = 0.0;
   int64_t cut_launches = 0;
+  // model spectra (gpdla_engine_model_spectra): a batch's absorbers, capacity offsets and outputs in one block
+  // carved in 256-byte steps, the kernel's per-pixel workspace ([3][slots]) and its status word
+  char* d_ms = nullptr;
+  double* d_ms_scratch = nullptr;
+  int32_t* d_ms_status = nullptr;
+  size_t cap_ms = 0, cap_ms_scratch = 0, cap_ms_status = 0;
+  double model_spectra_ms = 0.0;
+  int64_t model_spectra_launches = 0;
 
   std::vector<TimedLaunch> pending;
   gpdla_stats stats{};
@@ -297,6 +306,7 @@ int resolve_events(gpdla_engine* e) {
     if (t.kind == 12) { e->level_population_ms += ms; e->level_population_launches++; }
     if (t.kind == 13) { e->interval_ms += ms; e->interval_launches++; }
     if (t.kind == 14) { e->cut_ms += ms; e->cut_launches++; }
+    if (t.kind == 15) { e->model_spectra_ms += ms; e->model_spectra_launches++; }
     if (t.level >= 1 && t.level <= GPDLA_MAX_DLAS) {
       e->mstats.level_ms[t.level - 1] += ms;
       e->mstats.level_launches[t.level - 1]++;
@@ -406,7 +416,8 @@ void gpdla_engine_destroy(gpdla_engine* e) {
                   e->d_p_pdla, e->d_p_plane, e->d_p_lprob, e->d_p_lind, e->d_p_lbin,
                   e->d_lv_post, e->d_lv_planes, e->d_lv_plane, e->d_lv_lprob, e->d_lv_lind, e->d_lv_lbin,
                   e->d_i_lognhi, e->d_i_uniq, e->d_i_out, e->d_i_rank, e->d_i_count,
-                  e->d_c_zu, e->d_c_path[0], e->d_c_path[1], e->d_c_edges, e->d_c_np, e->d_c_wo, e->d_c_words};
+                  e->d_c_zu, e->d_c_path[0], e->d_c_path[1], e->d_c_edges, e->d_c_np, e->d_c_wo, e->d_c_words,
+                  e->d_ms, e->d_ms_scratch, e->d_ms_status};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (e->h_meta) (void)hipHostFree(e->h_meta);
@@ -1127,6 +1138,8 @@ int gpdla_engine_reset_stats(gpdla_engine* e) {
   e->interval_launches = 0;
   e->cut_ms = 0.0;
   e->cut_launches = 0;
+  e->model_spectra_ms = 0.0;
+  e->model_spectra_launches = 0;
   e->model_stats = gpdla_model_stats{};
   return GPDLA_OK;
 }
@@ -1193,13 +1206,150 @@ static int validate_summary_grid(const gpdla_summary_spec* spec) {
 // rows and base indices: the planes when spec has a grid, the posteriors and the split when pspec is given.
 // With cuts / cres (gpdla_engine_process_cuts) the search-cut launch runs per batch once its search ranges
 // exist and before the first grid reduction, which then all apply the cuts' sample tests.
+// One batch's model launch on the panel, padded wavelengths and SpecInfo resident in the engine: the absorbers
+// come from the caller (ab) or, in a search call, from the batch's evidences and MAP pairs (sel filled but for its
+// outputs, with the call's host levels / log priors).  Ends synchronised: its host staging is reused.
+struct ModelBatch {
+  int64_t q0, nq, slots;             // first spectrum, spectra, slot capacity of the batch
+  const gpdla_model_spectra* res;
+  const gpdla_model_absorbers* ab;   // stand-alone entry, or nullptr
+  ModelLevelArgs sel;                // search call: rows, levels, ll_dla, map_z, map_n
+  const int32_t* h_levels;           // search call: host [Q] given levels, or nullptr (best)
+  const double* h_lp;                // search call: host [D][Q] log priors, or nullptr
+  int64_t Q;
+};
+
+static int model_spectra_batch(gpdla_engine* e, const ModelBatch& b) {
+  const gpdla_model_spectra* res = b.res;
+  const int64_t q0 = b.q0, nq = b.nq, q1 = q0 + nq;
+  const bool out_dev = res->memory == GPDLA_MEM_DEVICE;
+  hipStream_t st = e->stream;
+  int rc;
+  const int D = b.ab ? 0 : b.sel.levels;
+  const int64_t c0 = res->cap_offsets[q0], ncap = res->cap_offsets[q1] - c0;
+  size_t off = 0;
+  auto carve = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+  const size_t o_cnt = carve((size_t)nq * 4), o_z = carve((size_t)nq * kMaxDlas * 8), o_n = carve((size_t)nq * kMaxDlas * 8),
+               o_lin = carve((size_t)nq * kMaxDlas * 8), o_cap = carve((size_t)(nq + 1) * 8),
+               o_giv = carve((size_t)nq * 4), o_lp = carve((size_t)nq * (D > 0 ? D : 1) * 8);
+  const size_t o_out = off;
+  const size_t o_pi = carve((size_t)ncap * 4), o_a = carve((size_t)ncap * 8), o_mm = carve((size_t)ncap * 8),
+               o_cm = carve((size_t)ncap * 8), o_sd = carve((size_t)ncap * 8), o_chi = carve((size_t)nq * 8),
+               o_ll = carve((size_t)nq * 8), o_np = carve((size_t)nq * 4), o_lv = carve((size_t)nq * 4);
+  if ((rc = grow(&e->d_ms, &e->cap_ms, off))) return rc;
+  if ((rc = grow(&e->d_ms_scratch, &e->cap_ms_scratch, (size_t)(3 * b.slots)))) return rc;
+  std::vector<int64_t> h_cap((size_t)nq + 1);
+  for (int64_t q = 0; q <= nq; ++q) h_cap[q] = res->cap_offsets[q0 + q] - c0;
+  HIP_TRY(hipMemcpyAsync(e->d_ms + o_cap, h_cap.data(), (size_t)(nq + 1) * 8, hipMemcpyHostToDevice, st));
+  // host results: the slots a spectrum does not fill come back as NaN / -1
+  if (!out_dev) HIP_TRY(hipMemsetAsync(e->d_ms + o_out, 0xFF, off - o_out, st));
+  bool lin = false;
+  if (b.ab) {
+    HIP_TRY(hipMemcpyAsync(e->d_ms + o_cnt, b.ab->counts + q0, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_ms + o_z, b.ab->z_dlas + q0 * kMaxDlas, (size_t)nq * kMaxDlas * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_ms + o_n, b.ab->log_nhis + q0 * kMaxDlas, (size_t)nq * kMaxDlas * 8, hipMemcpyHostToDevice, st));
+    if ((lin = b.ab->nhis != nullptr))
+      HIP_TRY(hipMemcpyAsync(e->d_ms + o_lin, b.ab->nhis + q0 * kMaxDlas, (size_t)nq * kMaxDlas * 8, hipMemcpyHostToDevice, st));
+  } else {
+    ModelLevelArgs sel = b.sel;
+    if (b.h_levels) {
+      HIP_TRY(hipMemcpyAsync(e->d_ms + o_giv, b.h_levels + q0, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+      sel.given = (const int32_t*)(e->d_ms + o_giv);
+    }
+    if (b.h_lp) {
+      for (int d = 0; d < D; ++d)
+        HIP_TRY(hipMemcpyAsync(e->d_ms + o_lp + (size_t)d * nq * 8, b.h_lp + (int64_t)d * b.Q + q0, (size_t)nq * 8,
+                               hipMemcpyHostToDevice, st));
+      sel.lp_dla = (const double*)(e->d_ms + o_lp);
+    }
+    sel.counts = (int32_t*)(e->d_ms + o_cnt); sel.z_dlas = (double*)(e->d_ms + o_z); sel.log_nhis = (double*)(e->d_ms + o_n);
+    sel.level_out = out_dev ? (res->levels ? res->levels + q0 : nullptr) : (int32_t*)(e->d_ms + o_lv);
+    HIP_TRY(launch_model_levels(sel, st));
+  }
+
+  ModelSpectraArgs ma{};
+  ma.q_count = (int32_t)nq; ma.info = e->d_info; ma.panel = e->d_panel; ma.lam_pad = e->d_lam; ma.slot_pixel = e->d_smap;
+  ma.num_lines = e->params.num_lines; ma.lines = make_line_args(e->d_lines);
+  ma.counts = (const int32_t*)(e->d_ms + o_cnt); ma.z_dlas = (const double*)(e->d_ms + o_z);
+  ma.log_nhis = (const double*)(e->d_ms + o_n); ma.nhis = lin ? (const double*)(e->d_ms + o_lin) : nullptr;
+  ma.cap_offsets = (const int64_t*)(e->d_ms + o_cap);
+  ma.scratch = e->d_ms_scratch; ma.scratch_plane = b.slots;
+  if (out_dev) {
+    ma.pixel_inds = res->pixel_inds + c0; ma.absorption = res->absorption + c0; ma.model_mean = res->model_mean + c0;
+    ma.continuum_mean = res->continuum_mean + c0; ma.continuum_sd = res->continuum_sd + c0;
+    ma.chi2 = res->chi2 + q0; ma.log_likelihood = res->log_likelihoods + q0; ma.num_pixels = res->num_pixels + q0;
+  } else {
+    ma.pixel_inds = (int32_t*)(e->d_ms + o_pi); ma.absorption = (double*)(e->d_ms + o_a);
+    ma.model_mean = (double*)(e->d_ms + o_mm); ma.continuum_mean = (double*)(e->d_ms + o_cm);
+    ma.continuum_sd = (double*)(e->d_ms + o_sd); ma.chi2 = (double*)(e->d_ms + o_chi);
+    ma.log_likelihood = (double*)(e->d_ms + o_ll); ma.num_pixels = (int32_t*)(e->d_ms + o_np);
+  }
+  ma.status = e->d_ms_status;
+  TimedLaunch t15{};
+  if ((rc = record_start(e, &t15, 15))) return rc;
+  HIP_TRY(launch_model_spectra(e->K, ma, st));
+  HIP_TRY(hipEventRecord(t15.stop, st));
+  e->pending.push_back(t15);
+  if (!out_dev) {
+    const hipMemcpyKind k = hipMemcpyDeviceToHost;
+    if (ncap) {
+      HIP_TRY(hipMemcpyAsync(res->pixel_inds + c0, e->d_ms + o_pi, (size_t)ncap * 4, k, st));
+      HIP_TRY(hipMemcpyAsync(res->absorption + c0, e->d_ms + o_a, (size_t)ncap * 8, k, st));
+      HIP_TRY(hipMemcpyAsync(res->model_mean + c0, e->d_ms + o_mm, (size_t)ncap * 8, k, st));
+      HIP_TRY(hipMemcpyAsync(res->continuum_mean + c0, e->d_ms + o_cm, (size_t)ncap * 8, k, st));
+      HIP_TRY(hipMemcpyAsync(res->continuum_sd + c0, e->d_ms + o_sd, (size_t)ncap * 8, k, st));
+    }
+    HIP_TRY(hipMemcpyAsync(res->chi2 + q0, e->d_ms + o_chi, (size_t)nq * 8, k, st));
+    HIP_TRY(hipMemcpyAsync(res->log_likelihoods + q0, e->d_ms + o_ll, (size_t)nq * 8, k, st));
+    HIP_TRY(hipMemcpyAsync(res->num_pixels + q0, e->d_ms + o_np, (size_t)nq * 4, k, st));
+    if (!b.ab && res->levels) HIP_TRY(hipMemcpyAsync(res->levels + q0, e->d_ms + o_lv, (size_t)nq * 4, k, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));   // the staging vector and the block are reused by the next batch
+  return GPDLA_OK;
+}
+
+// the call's status word after its last batch: GPDLA_EINVAL naming a spectrum over its capacity, GPDLA_ENUMERIC
+static int model_spectra_finish(gpdla_engine* e, int64_t Q, const gpdla_model_spectra* res) {
+  int32_t status = 0;
+  HIP_TRY(hipMemcpy(&status, e->d_ms_status, 4, hipMemcpyDeviceToHost));
+  if (status) HIP_TRY(hipMemset(e->d_ms_status, 0, 4));
+  if (status & 2) {
+    const bool out_dev = res->memory == GPDLA_MEM_DEVICE;
+    std::vector<int32_t> np((size_t)Q);
+    if (out_dev) HIP_TRY(hipMemcpy(np.data(), res->num_pixels, (size_t)Q * 4, hipMemcpyDeviceToHost));
+    int64_t over_q = -1;
+    for (int64_t q = 0; q < Q && over_q < 0; ++q)
+      if ((out_dev ? np[q] : res->num_pixels[q]) > res->cap_offsets[q + 1] - res->cap_offsets[q]) over_q = q;
+    return set_error(GPDLA_EINVAL, "model spectra: spectrum %lld has more likelihood pixels than its capacity %lld (nothing written for it)",
+                     (long long)over_q, (long long)(over_q >= 0 ? res->cap_offsets[over_q + 1] - res->cap_offsets[over_q] : -1));
+  }
+  if (status & 1) return set_error(GPDLA_ENUMERIC, "model spectra: non-positive pivot (outputs NaN)");
+  return GPDLA_OK;
+}
+
+// the arrays of a gpdla_model_spectra and its capacity offsets over Q spectra
+static int model_spectra_check_results(const gpdla_model_spectra* res, int64_t Q) {
+  if (res->memory != GPDLA_MEM_HOST && res->memory != GPDLA_MEM_DEVICE)
+    return set_error(GPDLA_EINVAL, "model spectra: results memory=%d", res->memory);
+  if (!res->cap_offsets || !res->pixel_inds || !res->absorption || !res->model_mean || !res->continuum_mean ||
+      !res->continuum_sd || !res->chi2 || !res->log_likelihoods || !res->num_pixels)
+    return set_error(GPDLA_EINVAL, "model spectra: null result array");
+  if (res->cap_offsets[0] < 0) return set_error(GPDLA_EINVAL, "model spectra: cap_offsets[0] < 0");
+  for (int64_t q = 0; q < Q; ++q)
+    if (res->cap_offsets[q + 1] < res->cap_offsets[q])
+      return set_error(GPDLA_EINVAL, "model spectra: cap_offsets not monotone at %lld", (long long)q);
+  return GPDLA_OK;
+}
+
+
 static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
                               const gpdla_results_multi* res, const gpdla_summary_spec* spec,
                               const gpdla_summaries* sums, const gpdla_sub_dla* sub = nullptr,
                               const gpdla_results_sub* rsub = nullptr, const gpdla_population_spec* pspec = nullptr,
                               const gpdla_population* pop = nullptr, const gpdla_level_population* lv = nullptr,
                               const gpdla_interval_spec* ispec = nullptr, const gpdla_intervals* iv = nullptr,
-                              const gpdla_search_cuts* cuts = nullptr, const gpdla_search_cut_results* cres = nullptr) {
+                              const gpdla_search_cuts* cuts = nullptr, const gpdla_search_cut_results* cres = nullptr,
+                              const gpdla_model_levels* mlev = nullptr, const gpdla_model_spectra* mres = nullptr) {
   if (!e || !sp || !mu || !res) return set_error(GPDLA_EINVAL, "null argument");
   if (cuts) {   // (gpdla_engine_process_cuts: cres is set)
     if (!cres->z_uppers || !cres->pixel_counts || !cres->bitmap_offsets || !cres->bitmap_words)
@@ -1615,6 +1765,18 @@ static int process_multi_impl(gpdla_engine* e, const gpdla_spectra* sp, const gp
                                (size_t)nq * kSummaryPlanes * nbins * 8, sk, st));
     }
 
+    if (mlev) {   // (gpdla_engine_process_spectra_models: spec and mres are set) on the batch the sweeps just used
+      ModelBatch mb{};
+      mb.q0 = q0; mb.nq = nq; mb.Q = Q; mb.res = mres;
+      for (int64_t q = 0; q < nq; ++q)   // the batch's slot capacity, as gpdla_engine_process laid it out
+        mb.slots += 4 * ((sp->offsets[q0 + q + 1] - sp->offsets[q0 + q] + 3) / 4) + 4 * kChunkSteps;
+      mb.sel.rows = (int32_t)nq; mb.sel.levels = D; mb.sel.ll_dla = e->d_m_lldla;
+      mb.sel.map_z = e->d_s_z; mb.sel.map_n = e->d_s_n;
+      mb.h_levels = mlev->level_mode == GPDLA_MODEL_LEVEL_GIVEN ? mlev->levels : nullptr;
+      mb.h_lp = mlev->level_mode == GPDLA_MODEL_LEVEL_BEST ? mlev->log_priors_dla : nullptr;
+      if ((rc = model_spectra_batch(e, mb))) return rc;
+    }
+
     if (ispec) {
       const size_t Ss = (size_t)S, slots = (size_t)nq * D * kMaxDlas, nlev = (size_t)ispec->num_levels;
       if ((rc = grow(&e->d_i_out, &e->cap_i_out, slots * (8 + 2 * nlev)))) return rc;
@@ -1835,6 +1997,184 @@ int gpdla_engine_get_cut_stats(gpdla_engine* e, double* ms, int64_t* launches) {
   *ms = e->cut_ms;
   *launches = e->cut_launches;
   return GPDLA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// model spectra (include/gpdla.h "Model spectra"; kernel in model_spectra.hip)
+// ---------------------------------------------------------------------------------------------
+int gpdla_engine_get_model_spectra_stats(gpdla_engine* e, double* ms, int64_t* launches) {
+  if (!e || !ms || !launches) return set_error(GPDLA_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  int rc = resolve_events(e);
+  if (rc) return rc;
+  *ms = e->model_spectra_ms;
+  *launches = e->model_spectra_launches;
+  return GPDLA_OK;
+}
+
+int gpdla_engine_process_spectra_models(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_multi_dla* mu,
+                                        const gpdla_results_multi* res, const gpdla_summary_spec* spec,
+                                        const gpdla_summaries* sums, const gpdla_interval_spec* ispec,
+                                        const gpdla_intervals* iv, const gpdla_model_levels* mspec,
+                                        const gpdla_model_spectra* mres) {
+  if (!e || !sp || !mu || !spec || !sums || !mspec || !mres) return set_error(GPDLA_EINVAL, "null argument");
+  if ((ispec == nullptr) != (iv == nullptr)) return set_error(GPDLA_EINVAL, "interval spec and arrays go together");
+  if (e->gemm || e->i8)
+    return set_error(GPDLA_EUNSUPPORTED, "the model spectra need the fused fp64 path (this engine runs a panel-GEMM or int8 path)");
+  if (!model_spectra_supported(e->K)) return set_error(GPDLA_EUNSUPPORTED, "model spectra: rank %d is not compiled", e->K);
+  const int64_t Q = sp->num_spectra;
+  if (Q < 0) return set_error(GPDLA_EINVAL, "num_spectra < 0");
+  if (mspec->level_mode != GPDLA_MODEL_LEVEL_BEST && mspec->level_mode != GPDLA_MODEL_LEVEL_GIVEN)
+    return set_error(GPDLA_EINVAL, "model spectra: level_mode=%d", mspec->level_mode);
+  if (mspec->level_mode == GPDLA_MODEL_LEVEL_GIVEN) {
+    if (!mspec->levels) return set_error(GPDLA_EINVAL, "model spectra: null levels");
+    for (int64_t q = 0; q < Q; ++q)
+      if (mspec->levels[q] < 0 || mspec->levels[q] > mu->max_dlas)
+        return set_error(GPDLA_EINVAL, "model spectra: levels[%lld] = %d outside 0..%d", (long long)q, (int)mspec->levels[q],
+                         mu->max_dlas);
+  } else if (mu->max_dlas > 1 && !mspec->log_priors_dla) {
+    return set_error(GPDLA_EINVAL, "model spectra: the best level of max_dlas=%d needs log_priors_dla", mu->max_dlas);
+  }
+  if (Q > 0) {
+    if (!sp->offsets) return set_error(GPDLA_EINVAL, "null spectra array");
+    int rcr = model_spectra_check_results(mres, Q);
+    if (rcr) return rcr;
+    HIP_TRY(hipSetDevice(e->device));
+    int rcg = grow(&e->d_ms_status, &e->cap_ms_status, 1);
+    if (rcg) return rcg;
+    HIP_TRY(hipMemsetAsync(e->d_ms_status, 0, 4, e->stream));
+  }
+  const int rc = process_multi_impl(e, sp, mu, res, spec, sums, nullptr, nullptr, nullptr, nullptr, nullptr, ispec, iv,
+                                    nullptr, nullptr, mspec, mres);
+  if (rc < 0 || Q == 0) return rc;
+  const int rcm = model_spectra_finish(e, Q, mres);
+  return rcm ? rcm : rc;
+}
+
+int gpdla_engine_model_spectra(gpdla_engine* e, const gpdla_spectra* sp, const gpdla_model_absorbers* ab,
+                               const gpdla_model_spectra* res) {
+  if (!e || !sp || !ab || !res) return set_error(GPDLA_EINVAL, "null argument");
+  if (e->gemm || e->i8)
+    return set_error(GPDLA_EUNSUPPORTED, "the model spectra need the fused fp64 path (this engine runs a panel-GEMM or int8 path)");
+  if (!model_spectra_supported(e->K)) return set_error(GPDLA_EUNSUPPORTED, "model spectra: rank %d is not compiled", e->K);
+  const int64_t Q = sp->num_spectra;
+  if (Q < 0) return set_error(GPDLA_EINVAL, "num_spectra < 0");
+  if (Q == 0) return GPDLA_OK;
+  if (!sp->offsets || !sp->wavelengths || !sp->flux || !sp->noise_variance || !sp->pixel_mask || !sp->z_qsos)
+    return set_error(GPDLA_EINVAL, "null spectra array");
+  if (sp->memory != GPDLA_MEM_HOST && sp->memory != GPDLA_MEM_DEVICE) return set_error(GPDLA_EINVAL, "spectra memory=%d", sp->memory);
+  { const int rcr = model_spectra_check_results(res, Q); if (rcr) return rcr; }
+  if (!ab->counts || !ab->z_dlas || !ab->log_nhis) return set_error(GPDLA_EINVAL, "model spectra: null absorber array");
+  if (sp->offsets[0] < 0) return set_error(GPDLA_EINVAL, "offsets[0] < 0");
+  for (int64_t q = 0; q < Q; ++q) {
+    if (sp->offsets[q + 1] < sp->offsets[q]) return set_error(GPDLA_EINVAL, "offsets not monotone at %lld", (long long)q);
+    if (ab->counts[q] < 0 || ab->counts[q] > GPDLA_MAX_DLAS)
+      return set_error(GPDLA_EINVAL, "model spectra: counts[%lld] = %d outside 0..%d", (long long)q, (int)ab->counts[q],
+                       GPDLA_MAX_DLAS);
+  }
+  const bool in_dev = sp->memory == GPDLA_MEM_DEVICE, out_dev = res->memory == GPDLA_MEM_DEVICE;
+  HIP_TRY(hipSetDevice(e->device));
+  hipStream_t st = e->stream;
+  int rc;
+  // (pageable host staging below: every batch ends with a synchronisation)
+  HIP_TRY(hipStreamSynchronize(st));
+  if ((rc = grow(&e->d_ms_status, &e->cap_ms_status, 1))) return rc;
+  HIP_TRY(hipMemsetAsync(e->d_ms_status, 0, 4, st));
+
+  const int64_t QB = e->params.max_batch_spectra > 0 ? e->params.max_batch_spectra : 1024;
+  const int64_t row = panel_row_doubles(e->K);
+  const size_t per_batch = (size_t)(QB + 1) + 4 * (size_t)QB;   // gpdla_engine_process's metadata layout
+  std::vector<int64_t> hm(per_batch);
+  for (int64_t q0 = 0; q0 < Q; q0 += QB) {
+    const int64_t q1 = std::min(Q, q0 + QB), nq = q1 - q0;
+    int64_t* h_off = hm.data();
+    int64_t* h_sb = h_off + (QB + 1);
+    int64_t* h_lb = h_sb + QB;
+    int64_t* h_sc = h_lb + QB;
+    int64_t slots = 0, lams = 0;
+    for (int64_t q = 0; q < nq; ++q) {   // (as gpdla_engine_process lays a batch out)
+      h_off[q] = sp->offsets[q0 + q] - sp->offsets[q0];
+      const int64_t lpix = sp->offsets[q0 + q + 1] - sp->offsets[q0 + q];
+      const int64_t cap = 4 * ((lpix + 3) / 4) + 4 * kChunkSteps;
+      h_sb[q] = slots; h_lb[q] = lams; h_sc[q] = cap;
+      slots += cap;
+      lams += cap + 8;
+    }
+    h_off[nq] = sp->offsets[q1] - sp->offsets[q0];
+    const int64_t npix = h_off[nq], pbase = sp->offsets[q0];
+    if ((rc = grow(&e->d_meta, &e->cap_meta, per_batch))) return rc;
+    if ((rc = grow(&e->d_info, &e->cap_q, (size_t)QB))) return rc;
+    if ((rc = grow(&e->d_panel, &e->cap_slots, (size_t)(slots * row + panel_lds_row_doubles(e->K))))) return rc;
+    if ((rc = grow(&e->d_lam, &e->cap_lam, (size_t)lams))) return rc;
+    if ((rc = grow(&e->d_smap, &e->cap_smap, (size_t)slots))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_meta, hm.data(), per_batch * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    const double *wl, *fl, *nv, *zq;
+    const uint8_t* mk;
+    if (in_dev) {
+      wl = sp->wavelengths + pbase; fl = sp->flux + pbase; nv = sp->noise_variance + pbase;
+      mk = sp->pixel_mask + pbase; zq = sp->z_qsos + q0;
+    } else {
+      if ((rc = grow(&e->d_wl, &e->cap_wl, (size_t)npix))) return rc;
+      if ((rc = grow(&e->d_flux, &e->cap_flux, (size_t)npix))) return rc;
+      if ((rc = grow(&e->d_noise, &e->cap_noise, (size_t)npix))) return rc;
+      if ((rc = grow(&e->d_mask, &e->cap_mask, (size_t)npix))) return rc;
+      if ((rc = grow(&e->d_z, &e->cap_z, (size_t)nq))) return rc;
+      HIP_TRY(hipMemcpyAsync(e->d_wl, sp->wavelengths + pbase, npix * 8, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(e->d_flux, sp->flux + pbase, npix * 8, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(e->d_noise, sp->noise_variance + pbase, npix * 8, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(e->d_mask, sp->pixel_mask + pbase, npix, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(e->d_z, sp->z_qsos + q0, nq * 8, hipMemcpyHostToDevice, st));
+      wl = e->d_wl; fl = e->d_flux; nv = e->d_noise; mk = e->d_mask; zq = e->d_z;
+    }
+    PrepArgs pa{};
+    pa.q_count = (int32_t)nq;
+    pa.offsets = e->d_meta;
+    pa.wavelengths = wl; pa.flux = fl; pa.noise = nv; pa.mask = mk; pa.z_qsos = zq;
+    pa.slot_base = e->d_meta + (QB + 1);
+    pa.lam_base = pa.slot_base + QB;
+    pa.slot_cap = pa.lam_base + QB;
+    pa.num_rest = e->num_rest;
+    pa.rest = e->d_rest; pa.mu = e->d_mu; pa.M_rowmajor = e->d_M; pa.log_omega = e->d_logom;
+    pa.c_0 = e->c0; pa.tau_0 = e->tau0; pa.beta = e->beta;
+    pa.min_lambda = e->params.min_lambda; pa.max_lambda = e->params.max_lambda;
+    pa.lya = e->params.lya_wavelength; pa.lyman_limit = e->params.lyman_limit;
+    pa.min_z_cut = e->params.min_z_cut; pa.max_z_cut = e->params.max_z_cut;
+    pa.pixel_spacing = e->params.pixel_spacing;
+    pa.absorption_mode = e->params.absorption_mode;
+    pa.om2_hi_e = e->om2_hi_e;
+    pa.info = e->d_info; pa.panel = e->d_panel; pa.lam_pad = e->d_lam; pa.slot_pixel = e->d_smap;
+    pa.k = e->K;
+    TimedLaunch t0{};
+    if ((rc = record_start(e, &t0, 0))) return rc;
+    HIP_TRY(launch_prep(e->K, pa, st));
+    HIP_TRY(hipEventRecord(t0.stop, st));
+    e->pending.push_back(t0);
+    if (e->forest_on) {   // as gpdla_engine_process applies it
+      ForestArgs fa{};
+      fa.q_count = (int32_t)nq; fa.info = e->d_info; fa.offsets = e->d_meta; fa.wavelengths = wl; fa.z_qsos = zq;
+      fa.slot_cap = pa.slot_cap; fa.slot_pixel = e->d_smap;
+      fa.num_rest = e->num_rest; fa.rest = e->d_rest; fa.log_omega = e->d_logom;
+      fa.c_0 = e->c0; fa.tau_0 = e->tau0; fa.beta = e->beta;
+      fa.mf_tau_0 = e->forest.mean_flux_tau_0; fa.mf_beta = e->forest.mean_flux_beta;
+      fa.num_lines = e->forest.num_forest_lines;
+      fa.variance_series = e->forest.variance_series != 0; fa.mean_flux = e->forest.mean_flux != 0;
+      fa.mean_flux_scope = e->forest_scope;
+      fa.panel = e->d_panel;
+      TimedLaunch t8{};
+      if ((rc = record_start(e, &t8, 8))) return rc;
+      HIP_TRY(launch_forest(e->K, fa, st));
+      if (e->forest_scope != 0) HIP_TRY(launch_forest_covariance(e->K, fa, st));
+      HIP_TRY(hipEventRecord(t8.stop, st));
+      e->pending.push_back(t8);
+    }
+
+    ModelBatch mb{};
+    mb.q0 = q0; mb.nq = nq; mb.slots = slots; mb.res = res; mb.ab = ab;
+    if ((rc = model_spectra_batch(e, mb))) return rc;
+  }
+  if ((rc = resolve_events(e))) return rc;
+  return model_spectra_finish(e, Q, res);
 }
 
 int gpdla_engine_get_level_population_stats(gpdla_engine* e, double* ms, int64_t* launches) {

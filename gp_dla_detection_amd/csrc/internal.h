@@ -731,6 +731,52 @@ hipError_t launch_forest_covariance(int K, const ForestArgs& a, hipStream_t s);
 hipError_t launch_forest_f64(const double* wl, int64_t n, double z_qso, double tau_0, double beta, int32_t L,
                              double* out, hipStream_t s);
 
+// ---- model spectra (model_spectra.hip): one workgroup per spectrum of a batch whose
+// slot panel, padded wavelengths and SpecInfo are resident (after prep_kernel and the forest launches)
+struct ModelSpectraArgs {
+  int32_t q_count;
+  const SpecInfo* info;
+  const double* panel;           // fused fp64 layout
+  const double* lam_pad;
+  const int32_t* slot_pixel;     // prep_kernel's position -> pixel map
+  int32_t num_lines;
+  LineArgs lines;
+  const int32_t* counts;         // [q_count] absorbers 0..kMaxDlas
+  const double* z_dlas;          // [q_count][kMaxDlas]
+  const double* log_nhis;        // [q_count][kMaxDlas] log10 N_HI
+  const double* nhis;            // [q_count][kMaxDlas] N_HI (cm^-2), or nullptr: exp10(log_nhis) on the device
+  const int64_t* cap_offsets;    // [q_count + 1] where a spectrum's per-pixel values go, and how many fit
+  double* scratch;               // [3][slot capacity of the batch], read only by spectra over GPDLA_MODEL_SPECTRA_LDS
+  int64_t scratch_plane;         // doubles per plane of scratch
+  int32_t* pixel_inds;           // per pixel, at cap_offsets[q] + 0 .. n - 1
+  double *absorption, *model_mean, *continuum_mean, *continuum_sd;
+  double *chi2, *log_likelihood; // [q_count]
+  int32_t* num_pixels;           // [q_count]
+  int32_t* status;               // bit 0: a pivot of B not positive; bit 1: a spectrum over its capacity
+};
+// The absorbers of a searched batch (gpdla_engine_process_spectra_models): per spectrum the level -- given, or
+// the DLA level d in 1..levels with the largest ll_dla[d - 1] + lp_dla[d - 1] (first maximum, NaN ignored, level 1
+// when every one is NaN: catalog.absorber_table's rule) -- and that level's MAP pairs of the summary launch
+struct ModelLevelArgs {
+  int32_t rows, levels;          // spectra of the batch, D
+  const double* ll_dla;          // [levels][rows] evidences
+  const double* lp_dla;          // [levels][rows] log priors, or nullptr (all equal)
+  const int32_t* given;          // [rows] levels 0..D, or nullptr: the best
+  const double* map_z;           // [levels][rows][kMaxDlas]
+  const double* map_n;           // [levels][rows][kMaxDlas] log10 N_HI
+  int32_t* counts;               // [rows] out = the level
+  double* z_dlas;                // [rows][kMaxDlas] out
+  double* log_nhis;              // [rows][kMaxDlas] out
+  int32_t* level_out;            // [rows] out, or nullptr
+};
+hipError_t launch_model_levels(const ModelLevelArgs& a, hipStream_t s);
+// the ranks the fused fp64 kernels are compiled for (kernels.hip, multi_dla.hip and forest.hip spell the same list)
+#ifndef GPDLA_FOR_EACH_RANK
+#define GPDLA_FOR_EACH_RANK(X) X(4) X(8) X(10) X(12) X(16) X(20) X(24)
+#endif
+bool model_spectra_supported(int K);
+hipError_t launch_model_spectra(int K, const ModelSpectraArgs& a, hipStream_t s);
+
 // host-side table fitting (faddeeva_host.cpp)
 void fit_core_table(int line, double* core);
 void fit_wing_line(int line, double* wing);

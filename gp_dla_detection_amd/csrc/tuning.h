@@ -76,3 +76,12 @@
 #ifndef GPDLA_MIX_TAPS
 #define GPDLA_MIX_TAPS 256
 #endif
+
+// model_spectra_kernel (model_spectra.hip): pixel positions of one spectrum whose per-pixel weights (a^2 / d,
+// a r / d, a: 24 bytes each) stay in LDS between the kernel's passes; a longer spectrum keeps them in its
+// stretch of a global workspace.  Not swept.  At 1e-4 dex the modelled range holds at most 1,250 pixels, so
+// 1,024 keeps all but the longest spectra in LDS and lets the tests reach the workspace path with a spectrum
+// of the usual kind (n = 1,100).
+#ifndef GPDLA_MODEL_SPECTRA_LDS
+#define GPDLA_MODEL_SPECTRA_LDS 1024
+#endif

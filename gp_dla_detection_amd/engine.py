@@ -54,6 +54,61 @@ def _params_struct(p: Parameters, max_batch_spectra: int = 0, path: str = "auto"
                     max_batch_spectra=max_batch_spectra, path=_PATHS[path])
 
 
+# relative guard band of model_capacities' rest-wavelength test: far above the rounding of lambda / (1 + z)
+# (a few 1e-16), far below a pixel (2.3e-4)
+MODEL_CAPACITY_GUARD = 1e-12
+
+
+def model_capacities(packed: dict, params: Parameters) -> np.ndarray:
+    """An upper bound [Q] on each spectrum's likelihood pixels: its pixels with min_lambda (1 - g) <= lambda /
+    (1 + z_qso) <= max_lambda (1 + g), g = MODEL_CAPACITY_GUARD, the mask ignored.  The device's own test is
+    the same without the guard band, so however the division rounds, n <= capacity."""
+    offsets = np.asarray(packed["offsets"], dtype=np.int64)
+    wl = np.asarray(packed["wavelengths"], dtype=np.float64)
+    zq = np.asarray(packed["z_qsos"], dtype=np.float64)
+    caps = np.zeros(offsets.size - 1, dtype=np.int64)
+    lo, hi = params.min_lambda * (1 - MODEL_CAPACITY_GUARD), params.max_lambda * (1 + MODEL_CAPACITY_GUARD)
+    for q in range(caps.size):
+        rest = wl[offsets[q]:offsets[q + 1]] / (1 + zq[q])
+        caps[q] = np.count_nonzero((rest >= lo) & (rest <= hi))
+    return caps
+
+
+def _absorber_arrays(Q: int, z_dlas, log_nhis, counts):
+    """[Q][4] NaN-padded z and log N_HI and the int32 counts of Engine.model_spectra; ValueError for a shape that
+    does not fit or a count outside 0..4."""
+    z, n = np.asarray(z_dlas, dtype=np.float64), np.asarray(log_nhis, dtype=np.float64)
+    z = z.reshape(Q, -1) if z.size else np.zeros((Q, 0))
+    n = n.reshape(Q, -1) if n.size else np.zeros((Q, 0))
+    if z.shape != n.shape or z.shape[1] > L.MAX_DLAS:
+        raise ValueError(f"z_dlas and log_nhis must both be [Q][<= {L.MAX_DLAS}]")
+    z4, n4 = np.full((Q, L.MAX_DLAS), np.nan), np.full((Q, L.MAX_DLAS), np.nan)
+    z4[:, :z.shape[1]] = z
+    n4[:, :n.shape[1]] = n
+    if counts is None:
+        ok = np.isfinite(z4) & np.isfinite(n4)
+        cnt = np.where(ok.all(axis=1), L.MAX_DLAS, np.argmin(ok, axis=1)).astype(np.int32)
+    else:
+        cnt = np.ascontiguousarray(counts, dtype=np.int32).ravel()
+        if cnt.size != Q or np.any(cnt < 0) or np.any(cnt > np.minimum(L.MAX_DLAS, max(z.shape[1], 0))):
+            raise ValueError(f"counts must be Q integers in 0..{L.MAX_DLAS} and within the rows given")
+    return z4, n4, cnt
+
+
+def compact_model_spectra(cap_offsets, num_pixels, pixel_inds, arrays: dict) -> dict:
+    """The capacity-CSR of gpdla_engine_model_spectra squeezed to n_q values per spectrum: ``offsets`` [Q + 1]
+    and every flat array with its first num_pixels[q] values of each spectrum's stretch."""
+    npix = np.asarray(num_pixels, dtype=np.int64)
+    off = np.zeros(npix.size + 1, dtype=np.int64)
+    np.cumsum(npix, out=off[1:])
+    take = np.concatenate([cap_offsets[q] + np.arange(npix[q]) for q in range(npix.size)] or
+                          [np.zeros(0, dtype=np.int64)]).astype(np.int64)
+    out = dict(offsets=off, pixel_inds=np.asarray(pixel_inds)[take])
+    for key, arr in arrays.items():
+        out[key] = np.asarray(arr)[take]
+    return out
+
+
 def host_empty(shape: tuple, dtype=np.float64) -> np.ndarray:
     """An uninitialised host array for outputs the engine writes in full: the 13 GB full-DR12Q Q x S
     sample array is not NaN-filled first (a whole extra pass over it; the D2H copies touch each page
@@ -245,7 +300,7 @@ class Engine:
 
     def _run_multi(self, packed, max_dlas, resample_uniforms, base_sample_inds, want_samples, min_z_separation,
                    occam_log_penalty, raise_numeric, memory, summary, sub=None, models=False, population=None,
-                   levels=None, intervals=None, cuts=None) -> dict:
+                   levels=None, intervals=None, cuts=None, model_spectra=None) -> dict:
         """process_multi / process_summaries / process_models / process_population: ``summary`` is None or
         the samples' log N_HI and the grid; ``sub`` None or the sub-DLA column densities (``nhi``) and, for the
         MAP outputs, their log10 (``log_nhi``); ``models`` routes the call through gpdla_engine_process_models,
@@ -318,6 +373,27 @@ class Engine:
                         z_dla_quantiles=np.full(slot + (max(nlq, 1),), np.nan),
                         log_nhi_quantiles=np.full(slot + (max(nlq, 1),), np.nan),
                         lr_counts=np.zeros((Dc, Q), dtype=np.int32))
+
+        mlev = mres = None
+        if model_spectra is not None:
+            if spec is None or sub is not None or models or population is not None or levels or cuts is not None:
+                raise ValueError("model_spectra goes with the summaries and intervals (not sub_dla, population, levels or cuts)")
+            caps = model_spectra["capacities"]
+            m_cap = np.zeros(Q + 1, dtype=np.int64)
+            np.cumsum(caps, out=m_cap[1:])
+            tot = max(int(m_cap[-1]), 1)
+            m_pix = np.full(tot, -1, dtype=np.int32)
+            m_arr = {k: np.full(tot, np.nan) for k in ("absorption", "model_mean", "continuum", "continuum_sd")}
+            m_q = dict(chi2=np.full(Q, np.nan), log_likelihoods=np.full(Q, np.nan), num_pixels=np.zeros(Q, dtype=np.int32),
+                       levels=np.full(Q, -1, dtype=np.int32))
+            m_given, m_lp = model_spectra["levels"], model_spectra["log_priors_dla"]
+            mlev = L.ModelLevels(level_mode=L.MODEL_LEVEL_BEST if m_given is None else L.MODEL_LEVEL_GIVEN,
+                                 levels=L.ptr(m_given, C.c_int32), log_priors_dla=L.ptr(m_lp))
+            mres = L.ModelSpectra(memory=L.MEM_HOST, cap_offsets=L.ptr(m_cap, C.c_int64), pixel_inds=L.ptr(m_pix, C.c_int32),
+                                  absorption=L.ptr(m_arr["absorption"]), model_mean=L.ptr(m_arr["model_mean"]),
+                                  continuum_mean=L.ptr(m_arr["continuum"]), continuum_sd=L.ptr(m_arr["continuum_sd"]),
+                                  chi2=L.ptr(m_q["chi2"]), log_likelihoods=L.ptr(m_q["log_likelihoods"]),
+                                  num_pixels=L.ptr(m_q["num_pixels"], C.c_int32), levels=L.ptr(m_q["levels"], C.c_int32))
 
         def results_intervals(mem, get):
             return L.Intervals(memory=mem, z_means=get("z_dla_means"), z_sds=get("z_dla_sds"),
@@ -427,6 +503,11 @@ class Engine:
                                 map_log_nhi_lls=get("MAP_log_nhi_lls"))
 
         def call(sp, rs, sm, rsub=None, rpop=None, rlv=None, riv=None, rcut=None):
+            if mlev is not None:
+                return self.lib.gpdla_engine_process_spectra_models(
+                    self._h, C.byref(sp), C.byref(md), C.byref(rs), C.byref(spec), C.byref(sm),
+                    C.byref(ispec) if ispec is not None else None, C.byref(riv) if riv is not None else None,
+                    C.byref(mlev), C.byref(mres))
             if cspec is not None:
                 return self.lib.gpdla_engine_process_cuts(
                     self._h, C.byref(sp), C.byref(md), C.byref(subs) if subs is not None else None, C.byref(rs),
@@ -555,6 +636,12 @@ class Engine:
         if cspec is not None:
             cout["cut_bitmap_words"] = cout["cut_bitmap_words"][:int(cout["cut_bitmap_offsets"][-1])]
             out.update(cout, cut_proximity_zone=float(cuts["proximity_zone"]), cut_noise_thresh=float(cuts["noise_thresh"]))
+        if mlev is not None:
+            ms = compact_model_spectra(m_cap, m_q["num_pixels"], m_pix, m_arr)
+            out.update(model_offsets=ms["offsets"], model_pixel_inds=ms["pixel_inds"], model_absorption=ms["absorption"],
+                       model_mean=ms["model_mean"], model_continuum=ms["continuum"], model_continuum_sd=ms["continuum_sd"],
+                       model_levels=m_q["levels"], model_log_likelihoods=m_q["log_likelihoods"], model_chi2=m_q["chi2"],
+                       model_num_pixels=m_q["num_pixels"])
         if ispec is not None:
             for key, v in iout.items():   # the C arrays are GPDLA_MAX_DLAS slots wide
                 out[key] = v if key == "lr_counts" else np.ascontiguousarray(v[:, :, :Dc])
@@ -734,6 +821,124 @@ class Engine:
         return self._process_models(packed, max_dlas, None, log_nhi_samples, z_edges, log_nhi_edges, None, want_samples,
                                     "population", self._population_dict(population), kwargs, levels=halves,
                                     cuts=normalise_cuts(cuts))
+
+    # --------------------------------------------------------------------------- model spectra
+    def model_spectra(self, packed: dict, z_dlas, log_nhis, counts=None, nhis=None, capacities=None) -> dict:
+        """gpdla_engine_model_spectra: the model of the given absorbers on every spectrum's likelihood pixels,
+        without a search.  ``z_dlas`` / ``log_nhis`` are [Q][<= 4] (NaN-padded rows are fine with ``counts``);
+        ``counts`` [Q] defaults to the number of leading finite pairs of each row; ``nhis`` (optional) gives the
+        column densities themselves instead of 10**log_nhis.  Returns the compacted CSR: ``offsets`` [Q + 1],
+        ``pixel_inds`` (index within the spectrum), ``absorption``, ``model_mean``, ``continuum``,
+        ``continuum_sd`` (flat), and ``chi2``, ``log_likelihoods``, ``num_pixels`` per spectrum.  The posterior
+        absorbed fit is absorption * continuum.  ``capacities`` [Q] overrides the per-spectrum capacity
+        (default: ``model_capacities``); a spectrum over its capacity raises GpdlaError, whose ``partial``
+        attribute holds the result with that spectrum empty."""
+        offsets = np.ascontiguousarray(packed["offsets"], dtype=np.int64)
+        Q = offsets.size - 1
+        wl = np.ascontiguousarray(packed["wavelengths"], dtype=np.float64)
+        fl = np.ascontiguousarray(packed["flux"], dtype=np.float64)
+        nv = np.ascontiguousarray(packed["noise_variance"], dtype=np.float64)
+        mk = np.ascontiguousarray(packed["pixel_mask"], dtype=np.uint8)
+        zq = np.ascontiguousarray(packed["z_qsos"], dtype=np.float64)
+        if not (wl.size == fl.size == nv.size == mk.size and offsets[-1] <= wl.size and zq.size == Q):
+            raise ValueError("inconsistent spectra arrays")
+        z4, n4, cnt = _absorber_arrays(Q, z_dlas, log_nhis, counts)
+        lin = None
+        if nhis is not None:
+            lin = np.full((Q, L.MAX_DLAS), np.nan)
+            src = np.asarray(nhis, dtype=np.float64).reshape(Q, -1)
+            lin[:, :src.shape[1]] = src
+        caps = model_capacities(packed, self.params) if capacities is None else np.asarray(capacities, dtype=np.int64)
+        if caps.shape != (Q,) or np.any(caps < 0):
+            raise ValueError("capacities must be Q non-negative integers")
+        cap_off = np.zeros(Q + 1, dtype=np.int64)
+        np.cumsum(caps, out=cap_off[1:])
+        tot = max(int(cap_off[-1]), 1)
+        pix = np.full(tot, -1, dtype=np.int32)
+        arrs = {k: np.full(tot, np.nan) for k in ("absorption", "model_mean", "continuum", "continuum_sd")}
+        chi2, ll, npix = np.full(Q, np.nan), np.full(Q, np.nan), np.zeros(Q, dtype=np.int32)
+        sp = L.Spectra(memory=L.MEM_HOST, num_spectra=Q, offsets=L.ptr(offsets, C.c_int64),
+                       wavelengths=L.ptr(wl), flux=L.ptr(fl), noise_variance=L.ptr(nv),
+                       pixel_mask=L.ptr(mk, C.c_uint8), z_qsos=L.ptr(zq))
+        ab = L.ModelAbsorbers(counts=L.ptr(cnt, C.c_int32), z_dlas=L.ptr(z4), log_nhis=L.ptr(n4), nhis=L.ptr(lin))
+        rs = L.ModelSpectra(memory=L.MEM_HOST, cap_offsets=L.ptr(cap_off, C.c_int64), pixel_inds=L.ptr(pix, C.c_int32),
+                            absorption=L.ptr(arrs["absorption"]), model_mean=L.ptr(arrs["model_mean"]),
+                            continuum_mean=L.ptr(arrs["continuum"]), continuum_sd=L.ptr(arrs["continuum_sd"]),
+                            chi2=L.ptr(chi2), log_likelihoods=L.ptr(ll), num_pixels=L.ptr(npix, C.c_int32))
+        rc = self.lib.gpdla_engine_model_spectra(self._h, C.byref(sp), C.byref(ab), C.byref(rs))
+        written = rc in (L.GPDLA_OK, L.GPDLA_ENUMERIC) or (rc == L.GPDLA_EINVAL and np.any(npix > caps))
+        out = None
+        if written:
+            out = compact_model_spectra(cap_off, np.where(npix > caps, 0, npix), pix, arrs)
+            out.update(chi2=chi2, log_likelihoods=ll, num_pixels=npix)
+        if rc == L.GPDLA_ENUMERIC:
+            out["numeric_warning"] = self.lib.gpdla_last_error().decode()
+        elif rc != L.GPDLA_OK:
+            try:
+                L.check(rc)
+            except L.GpdlaError as err:
+                err.partial = out
+                raise
+        return out
+
+    def process_model_spectra(self, packed: dict, max_dlas: int, log_nhi_samples, level="best", log_priors_dla=None,
+                              z_edges=None, log_nhi_edges=None, want_samples: bool = False, intervals=None,
+                              **kwargs) -> dict:
+        """``process_summaries`` -- with ``intervals`` (True, or dict(levels=..., lr_delta=...)) ``process_intervals``
+        -- (same arguments, same outputs bit for bit) plus the model spectra of each
+        spectrum's level, rendered per device batch on the panel the sweeps just used
+        (gpdla_engine_process_spectra_models).  ``level``: "best" (the DLA level 1..max_dlas with the highest model
+        posterior, taken on the device from the evidences and ``log_priors_dla`` (max_dlas x Q; not needed with
+        max_dlas = 1): the level ``catalog.absorber_table`` takes), an integer 0..max_dlas for every spectrum (0: the
+        null model) or Q of them.  Adds ``model_offsets`` (Q + 1), ``model_pixel_inds``, ``model_absorption``,
+        ``model_mean``, ``model_continuum``, ``model_continuum_sd`` (flat, CSR by ``model_offsets``),
+        ``model_levels``, ``model_log_likelihoods``, ``model_chi2`` and ``model_num_pixels`` (Q); bitwise what
+        ``model_spectra`` gives for the level's ``MAP_z_dlas`` / ``MAP_log_nhis``."""
+        if (z_edges is None) != (log_nhi_edges is None):
+            raise ValueError("z_edges and log_nhi_edges go together")
+        lognhi = np.ascontiguousarray(log_nhi_samples, dtype=np.float64).ravel()
+        if lognhi.size != self.num_samples:
+            raise ValueError("one log_nhi sample per engine sample")
+        Q, D = np.asarray(packed["offsets"]).size - 1, int(max_dlas)
+        given = lp = None
+        if isinstance(level, str):
+            if level != "best":
+                raise ValueError(f"level must be 'best', an integer 0..max_dlas or Q of them, not {level!r}")
+            if D > 1:
+                if log_priors_dla is None:
+                    raise ValueError("level='best' with max_dlas > 1 needs log_priors_dla (max_dlas x Q)")
+                lp = np.ascontiguousarray(log_priors_dla, dtype=np.float64)
+                if lp.shape != (D, Q):
+                    raise ValueError(f"log_priors_dla must be {(D, Q)}")
+        else:
+            lv = np.asarray(level)
+            if lv.dtype.kind not in "iu" or lv.shape not in ((), (Q,)) or np.any(lv < 0) or np.any(lv > D):
+                raise ValueError(f"level must be 'best', an integer 0..{D} or {Q} of them")
+            given = np.ascontiguousarray(np.broadcast_to(lv, (Q,)), dtype=np.int32)
+        summary = dict(log_nhi=lognhi,
+                       z_edges=None if z_edges is None else np.ascontiguousarray(z_edges, dtype=np.float64).ravel(),
+                       n_edges=None if log_nhi_edges is None else np.ascontiguousarray(log_nhi_edges, dtype=np.float64).ravel())
+        order = ("resample_uniforms", "base_sample_inds", "min_z_separation", "occam_log_penalty", "raise_numeric", "memory")
+        unknown = set(kwargs) - set(order)
+        if unknown:
+            raise TypeError(f"unexpected keyword arguments {sorted(unknown)}")
+        ms = dict(levels=given, log_priors_dla=lp, capacities=model_capacities(packed, self.params))
+        ivs = None
+        if intervals is not None and intervals is not False:
+            ivd = {} if intervals is True else dict(intervals)
+            if set(ivd) - {"levels", "lr_delta"}:
+                raise ValueError("intervals must be True or dict(levels=..., lr_delta=...)")
+            ivs = dict(log_nhi=lognhi, levels=_interval_levels(ivd.get("levels")), lr_delta=float(ivd.get("lr_delta", 2.0)))
+        return self._run_multi(packed, max_dlas, kwargs.get("resample_uniforms"), kwargs.get("base_sample_inds"),
+                               want_samples, kwargs.get("min_z_separation"), kwargs.get("occam_log_penalty"),
+                               kwargs.get("raise_numeric", False), kwargs.get("memory", "host"), summary, intervals=ivs,
+                               model_spectra=ms)
+
+    def model_spectra_stats(self) -> dict:
+        """gpdla_engine_get_model_spectra_stats: cumulative ms and count of the model-spectra launches."""
+        ms, n = C.c_double(0.0), C.c_int64(0)
+        L.check(self.lib.gpdla_engine_get_model_spectra_stats(self._h, C.byref(ms), C.byref(n)))
+        return dict(model_spectra_ms=ms.value, model_spectra_launches=n.value)
 
     def cut_stats(self) -> dict:
         """gpdla_engine_get_cut_stats: cumulative ms and count of the search-cut launches."""

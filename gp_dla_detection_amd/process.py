@@ -370,7 +370,7 @@ def _compute_kwargs(max_dlas: int, summaries, save_samples: bool, sub=None, fore
 def _engine_compute(model: dict, samples: dict, packed: dict, params: Parameters, device: int = 0,
                     engine: Engine | None = None, max_dlas: int = 1, summaries=None, save_samples: bool = True,
                     timings: dict | None = None, sub_dla=None, forest=None, population=None, intervals=None,
-                    cuts=None) -> dict:
+                    cuts=None, model_spectra=None) -> dict:
     """The hot path on the GPU: per-spectrum null / sample / DLA log likelihoods and z ranges; with
     ``max_dlas`` > 1 every level of the multi-DLA search (Engine.process_multi's arrays); with
     ``summaries`` the posterior summaries as well (Engine.process_summaries), the sample arrays only if
@@ -388,6 +388,22 @@ def _engine_compute(model: dict, samples: dict, packed: dict, params: Parameters
     try:
         if forest is not None:
             eng.set_forest(forest)
+        if model_spectra is not None:   # (with the summaries alone: process_qsos has checked)
+            if "log_nhi_samples" not in samples:
+                raise ValueError("model_spectra needs samples['log_nhi_samples']")
+            res = eng.process_model_spectra(packed, max_dlas, samples["log_nhi_samples"], level=model_spectra["level"],
+                                            log_priors_dla=model_spectra["log_priors_dla"],
+                                            z_edges=grid[0] if grid else None, log_nhi_edges=grid[1] if grid else None,
+                                            want_samples=save_samples,
+                                            intervals=None if intervals is None else dict(levels=intervals["levels"],
+                                                                                          lr_delta=intervals["lr_delta"]))
+            if max_dlas == 1:   # Engine.process's shapes: no level axis, no multi-DLA variables
+                res["log_likelihoods_dla"] = res["log_likelihoods_dla"][0]
+                if "sample_log_likelihoods_dla" in res:
+                    res["sample_log_likelihoods_dla"] = res["sample_log_likelihoods_dla"][0]
+                res.pop("base_sample_inds", None)
+                res.pop("max_dlas", None)
+            return res
         if cuts is not None:
             if "log_nhi_samples" not in samples:
                 raise ValueError("cuts need samples['log_nhi_samples']")
@@ -716,7 +732,7 @@ def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
                  params: Parameters | None = None, test_ind=None, engine: Engine | None = None,
                  device: int = 0, metadata: dict | None = None, max_dlas: int = 1, compute=None,
                  summaries=None, save_samples: bool = True, sub_dla=None, forest=None, population=None,
-                 intervals=None, cuts=None) -> dict:
+                 intervals=None, cuts=None, model_spectra=None) -> dict:
     """Run the DLA search (process_qsos.m:88-232) and return the saved variables.  ``max_dlas`` > 1
     (up to 4) runs the multi-DLA search: ``log_likelihoods_dla`` / ``log_priors_dla`` /
     ``log_posteriors_dla`` become Q x D, ``model_posteriors`` Q x (1 + D), ``sample_log_likelihoods_dla``
@@ -788,9 +804,28 @@ def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
     thresholds None); with ``intervals`` or ``sub_dla`` it raises ValueError: the cuts do not cover the interval
     outputs or the sub-DLA model.  Every variable that is not a grid reduction is as before, bit for bit, and so
     is everything without the keyword.  A ``compute`` replacement receives ``cuts=`` (dict(proximity_zone,
-    noise_thresh, omega_m), NaN = off) and returns the ``cut_*`` arrays of Engine.process_cuts."""
+    noise_thresh, omega_m), NaN = off) and returns the ``cut_*`` arrays of Engine.process_cuts.
+
+    ``model_spectra`` (True, or ``dict(level=...)``) renders the model on the pixels per device batch, on the panel
+    the sweeps just used (Engine.process_model_spectra): ``level`` "best" (default: the DLA level with the highest
+    model posterior, the one ``MAP_z_dlas`` takes), an integer 0..max_dlas (0: the null model) or Q of them.  The
+    output and the file gain MODEL_SPECTRA_VARIABLES.  It implies ``summaries=True`` and composes with ``max_dlas``,
+    a summary grid, ``intervals``, ``forest`` and ``save_samples=False``; with ``sub_dla``, ``population``,
+    ``cuts``, summaries ``levels="all"`` or a ``compute`` replacement it raises ValueError.  Without the keyword
+    every variable and the file are as before, bit for bit."""
     if not 1 <= int(max_dlas) <= 4:
         raise ValueError("max_dlas must be 1..4")
+    msp = _model_spectra_spec(model_spectra)
+    if msp is not None:
+        for name, val in (("sub_dla", sub_dla), ("population", population), ("cuts", cuts)):
+            if val is not None and val is not False:
+                raise ValueError(f"model_spectra does not combine with {name} in the same call")
+        if compute is not None:
+            raise ValueError("model_spectra does not combine with a compute replacement")
+        if _summary_levels(summaries):
+            raise ValueError("model_spectra does not combine with summaries levels='all'")
+        if _summary_grid(summaries) is None:
+            summaries = True
     from .engine import normalise_cuts
     cts = normalise_cuts(cuts)
     if cts is not None:
@@ -818,12 +853,20 @@ def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
     if pop is not None:
         lp_no, lp_dla, lp_lls = _model_log_priors(packed["z_qsos"], prior, params, max_dlas, sub)
         popkw = dict(pop, log_priors_no_dla=lp_no, log_priors_dla=lp_dla, log_priors_lls=lp_lls)
+    if msp is not None:
+        lv = msp["level"]
+        if not isinstance(lv, str):
+            lv = np.asarray(lv)
+            if lv.dtype.kind not in "iu" or lv.shape not in ((), (packed["z_qsos"].size,)) or np.any(lv < 0) or np.any(lv > max_dlas):
+                raise ValueError(f"model_spectra level must be 'best', an integer 0..{int(max_dlas)} or one per spectrum")
+        msp = dict(level=lv, log_priors_dla=_model_log_priors(packed["z_qsos"], prior, params, max_dlas)[1])
     if compute is not None:
         res = compute(model, samples, packed, params, device,
                       **_compute_kwargs(max_dlas, summaries, save_samples, sub, fst, popkw, ivs, cts))
     else:
         res = _engine_compute(model, samples, packed, params, device, engine, max_dlas, summaries, save_samples,
-                              sub_dla=sub, forest=fst, population=popkw, intervals=ivs, cuts=cts)
+                              sub_dla=sub, forest=fst, population=popkw, intervals=ivs, cuts=cts,
+                              model_spectra=msp)
     if not save_samples:
         res = {k: v for k, v in res.items() if k not in ("sample_log_likelihoods_dla", "base_sample_inds",
                                                          "sample_log_likelihoods_lls")}
@@ -835,11 +878,33 @@ def process_qsos(model: dict, samples: dict, spectra, prior: dict | None = None,
     _finish_levels(out, res, summaries, pop, max_dlas)
     if cts is not None:
         _finish_cuts(out, res, cts, summaries, pop)
+    if msp is not None:
+        for key in MODEL_SPECTRA_VARIABLES:
+            out[key] = res[key]
     if test_ind is not None:
         out["test_ind"] = np.asarray(test_ind)
     return out
 
 
+def _model_spectra_spec(model_spectra):
+    """None, or dict(level=...) of process_qsos(model_spectra=...); ValueError for anything else."""
+    if model_spectra is None or model_spectra is False:
+        return None
+    if model_spectra is True:
+        return dict(level="best")
+    if not isinstance(model_spectra, dict) or set(model_spectra) - {"level"}:
+        raise ValueError("model_spectra must be None, True or dict(level=...)")
+    level = model_spectra.get("level", "best")
+    if isinstance(level, str) and level != "best":
+        raise ValueError(f"model_spectra level must be 'best', an integer or one per spectrum, not {level!r}")
+    return dict(level=level)
+
+
+# what a run with the model spectra saves besides (process_qsos(model_spectra=...)); catalog.py reads them.  The
+# per-pixel arrays are flat, CSR by model_offsets (Q + 1); the rest is per spectrum
+MODEL_SPECTRA_VARIABLES = ("model_offsets", "model_pixel_inds", "model_absorption", "model_mean", "model_continuum",
+                           "model_continuum_sd", "model_levels", "model_log_likelihoods", "model_chi2",
+                           "model_num_pixels")
 # names of process_qsos.m:235-243, in order
 PROCESSED_VARIABLES = ("training_release", "training_set_name", "dla_catalog_name", "prior_ind",
                        "release", "test_set_name", "test_ind", "prior_z_qso_increase", "max_z_cut",
@@ -908,7 +973,7 @@ def save_processed_qsos(path: str, out: dict, format: str = "v7.3") -> dict:
     multi = int(np.ravel(out.get("max_dlas", 1))[0]) > 1
     for key in (PROCESSED_VARIABLES + (MULTI_DLA_VARIABLES if multi else ()) + SUMMARY_VARIABLES + SUB_DLA_VARIABLES +
                 FOREST_VARIABLES + MEAN_FLUX_SCOPE_VARIABLES + POPULATION_VARIABLES + LEVEL_POPULATION_VARIABLES +
-                INTERVAL_VARIABLES + CUT_VARIABLES):
+                INTERVAL_VARIABLES + CUT_VARIABLES + MODEL_SPECTRA_VARIABLES):
         if key not in out:
             continue
         v = out[key]
@@ -1074,7 +1139,8 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
                      params: Parameters | None = None, device: int = 0, save: bool = True,
                      rank: int = 0, world: int = 1, compute=None, timings: dict | None = None,
                      chunk_rows: int | None = None, max_dlas: int = 1, summaries=None,
-                     save_samples: bool = True, sub_dla=None, forest=None, population=None) -> dict:
+                     save_samples: bool = True, sub_dla=None, forest=None, population=None,
+                     model_spectra=None) -> dict:
     """The whole ``process_qsos`` script (process_qsos.m:1-249) on files laid out as the reference
     lays them out (set_parameters.m:79-86):
 
@@ -1112,6 +1178,9 @@ def run_process_qsos(base_directory: str, training_release: str, training_set_na
     NotImplementedError: its arrays are not gathered); ``forest`` alone passes through to every rank's
     engine.  ``population`` as in ``process_qsos``, on one GPU only (``world`` > 1 raises NotImplementedError:
     its arrays are not gathered); ``levels="all"`` in either dict likewise."""
+    if model_spectra is not None and model_spectra is not False:
+        raise ValueError("model_spectra is not covered by run_process_qsos (nor by its multi-GPU split): "
+                         "call process_qsos and save_processed_qsos")
     import time
     if not 1 <= int(max_dlas) <= 4:
         raise ValueError("max_dlas must be 1..4")

@@ -871,6 +871,79 @@ int gpdla_engine_process_cuts(gpdla_engine* engine, const gpdla_spectra* spectra
 /* Cumulative kernel time (HIP events) and count of the search-cut launches since create / reset_stats. */
 int gpdla_engine_get_cut_stats(gpdla_engine* engine, double* ms, int64_t* launches);
 
+/* ---- Model spectra: absorption, GP continuum and goodness of fit on the pixels ---------
+ * For spectrum q and its counts[q] absorbers (z_dlas[q][i], log_nhis[q][i], i < counts[q]; 0: the null model), on
+ * the likelihood's n unmasked in-range pixels in pixel order, with mu, M, omega^2, y, sigma^2 as the sweeps see
+ * them (after the forest launches when a forest is set):
+ *   a       the product of the absorbers' Voigt profiles: num_lines lines, the padded grid and instrument
+ *           broadening of gpdla_voigt_f64, each absorber broadened on its own, params.absorption_mode indexing
+ *   d = a^2 omega^2 + sigma^2, r = y - a mu, V = diag(a) M, B = I + V'D^-1 V, u = V'D^-1 r, w = B^-1 u
+ *   absorption a_j; model_mean a_j mu_j; continuum_mean mu_j + M_j w; continuum_sd sqrt(M_j B^-1 M_j'), the
+ *   posterior sd of the low-rank continuum (the white omega term is not in it)
+ *   chi2 = r'D^-1 r - u'B^-1 u = r'K^-1 r;  log_likelihood = -(chi2 + log det B + sum log d_j + n log 2 pi) / 2
+ * Flux-like outputs are in the caller's units (a spectrum prep rescaled by a power of two is scaled back exactly).
+ * The per-pixel arrays are ragged: spectrum q's n_q values go to cap_offsets[q] + 0 .. n_q - 1, pixel_inds being
+ * each value's pixel index within the spectrum; num_pixels[q] = n_q.  cap_offsets[q + 1] - cap_offsets[q] must be
+ * at least n_q (the spectrum's in-range pixel count is an upper bound); what lies between n_q and the capacity is
+ * NaN / -1 with host results and untouched with device results.  A spectrum over its capacity is not written at
+ * all (NaN scalars, its num_pixels) and the call returns GPDLA_EINVAL naming it; the other spectra are complete.
+ * An absorber with a non-finite parameter gives NaN outputs for its spectrum, a spectrum without usable pixels NaN
+ * scalars and n = 0.  GPDLA_ENUMERIC: a pivot of B was not positive (that spectrum's outputs are NaN).
+ * Results are a function of the spectrum and its absorbers alone: repeated calls, any max_batch_spectra, host or
+ * device memory agree bit for bit.  GPDLA_EUNSUPPORTED on int8 and panel-GEMM engines. */
+typedef struct gpdla_model_absorbers {
+  const int32_t* counts;             /* host [Q], 0..GPDLA_MAX_DLAS */
+  const double* z_dlas;              /* host [Q][GPDLA_MAX_DLAS] */
+  const double* log_nhis;            /* host [Q][GPDLA_MAX_DLAS], log10 N_HI */
+  const double* nhis;                /* host [Q][GPDLA_MAX_DLAS] N_HI in cm^-2, or NULL: 10^log_nhis */
+} gpdla_model_absorbers;
+
+typedef struct gpdla_model_spectra {
+  int32_t memory;                    /* GPDLA_MEM_HOST or GPDLA_MEM_DEVICE: where the arrays below live */
+  const int64_t* cap_offsets;        /* host [Q + 1], ascending */
+  int32_t* pixel_inds;               /* [cap_offsets[Q]] */
+  double* absorption;
+  double* model_mean;
+  double* continuum_mean;
+  double* continuum_sd;
+  double* chi2;                      /* [Q] */
+  double* log_likelihoods;           /* [Q] */
+  int32_t* num_pixels;               /* [Q] */
+  int32_t* levels;                   /* [Q] the level drawn, written by gpdla_engine_process_spectra_models only; or NULL */
+} gpdla_model_spectra;
+
+/* prep_kernel (and the forest launches when set) on the given spectra, then the model-spectra kernel with the
+ * caller's absorbers: no search, no samples read. */
+int gpdla_engine_model_spectra(gpdla_engine* engine, const gpdla_spectra* spectra,
+                               const gpdla_model_absorbers* absorbers, const gpdla_model_spectra* results);
+/* The same launch inside a search: gpdla_engine_process_summaries -- or, with ispec and intervals set (both or
+ * neither), gpdla_engine_process_intervals -- (same arguments, same outputs bit for bit) and,
+ * per device batch after the summary launch, on the panel the sweeps just used, the model of each spectrum's level:
+ *   GPDLA_MODEL_LEVEL_BEST   the DLA level d in 1..max_dlas with the largest log_likelihoods_dla[d - 1][q] +
+ *                            log_priors_dla[d - 1][q] (the level of the highest model posterior; first maximum, NaN
+ *                            ignored, level 1 when all are NaN), taken on the device.  log_priors_dla may be NULL
+ *                            with max_dlas = 1
+ *   GPDLA_MODEL_LEVEL_GIVEN  levels[q] in 0..max_dlas (0: the null model)
+ * The absorbers are level d's d MAP pairs of the summaries (gpdla_summaries.map_z_dlas / map_log_nhis), N_HI =
+ * 10^log N_HI formed on the device exactly as gpdla_engine_model_spectra forms it without `nhis`, so the results are
+ * bitwise those of that call fed the same pairs.  A level without a MAP sample gives NaN outputs.  results->levels
+ * receives the level drawn.  Errors as gpdla_engine_model_spectra and gpdla_engine_process_summaries, and
+ * GPDLA_EINVAL for a level outside 0..max_dlas, NULL levels, or BEST with max_dlas > 1 and no priors. */
+#define GPDLA_MODEL_LEVEL_BEST 0
+#define GPDLA_MODEL_LEVEL_GIVEN 1
+typedef struct gpdla_model_levels {
+  int32_t level_mode;                /* GPDLA_MODEL_LEVEL_* */
+  const int32_t* levels;             /* host [Q] with GIVEN */
+  const double* log_priors_dla;      /* host [max_dlas][Q] with BEST */
+} gpdla_model_levels;
+int gpdla_engine_process_spectra_models(gpdla_engine* engine, const gpdla_spectra* spectra, const gpdla_multi_dla* multi,
+                                        const gpdla_results_multi* results_multi, const gpdla_summary_spec* spec,
+                                        const gpdla_summaries* summaries, const gpdla_interval_spec* ispec,
+                                        const gpdla_intervals* intervals, const gpdla_model_levels* levels,
+                                        const gpdla_model_spectra* results);
+/* Cumulative kernel time (HIP events) and count of the model-spectra launches since create / reset_stats. */
+int gpdla_engine_get_model_spectra_stats(gpdla_engine* engine, double* ms, int64_t* launches);
+
 /* ---- Count mixture: the total column of a redshift bin on a lattice -------------------
  * calc_cddf.py's _get_omega_confidence_intervals (:562-636) combines the count distributions of a redshift
  * bin's column-density bins into the distribution of T = sum_b n_b N_b.  Here T lives on a dense fp64 lattice of
